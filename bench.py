@@ -17,8 +17,13 @@ N > 1 GPUs (one process per GPU, torch.distributed): every rank encodes its own
 batch of independent squares -- the work partitions by square with no data-path
 exchange, so scaling is "weak".
 
-Extra JSON objects: "roofline" (dominant kernel, HIP-event timed on the launch
-stream), "step_roofline" (whole 2D encode vs SURVEY's algorithmic bytes 4k^2 S),
+A plain run sets up, warms up, times the steps and prints the result line with
+"roofline" (dominant kernel, HIP-event timed on the launch stream) and "step_roofline"
+(whole 2D encode vs SURVEY's algorithmic bytes 4k^2 S), both from the timed steps' own
+events.  --dump-outputs DIR also writes a seeded sample of the last timed step's EDS.
+
+--full adds the oracle gate on the first warm-up step, the isolated-launch timings in
+"step_roofline" and the extra JSON objects:
 "cpu_baseline" (the C restatement of the reference path -- AVX-512 + GFNI where the host has
 it, else AVX2 -- kind "port", on every CPU this process may run on: sched_getaffinity),
 "host_path" (PCIe-inclusive rates, pinned+overlapped and pageable; never `value`),
@@ -47,6 +52,15 @@ def parse():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     p.add_argument("--batch", type=int, default=0, help="squares per step (default: >= 1 GiB of EDS; steps rotate over --buffers batches, so a step never finds its squares in the 256 MiB Infinity Cache)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run everything else this file measures or checks: the oracle "
+                        "gate on the first warm-up step, the isolated-launch timings, the CPU baseline and the "
+                        "sub-lines (host path, codec, roots, c3, c4, c5, ...); the --no-* options and "
+                        "--headline-only trim that set.  Without it: set-up, warm-up, the timed steps, the "
+                        "result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write a fixed, seeded sample of the EDS the last timed step "
+                        "computed to DIR/eds_sample.npy (float32)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-c5", action="store_true", help="skip the config-5 (sharded 512x512 square) line")
     p.add_argument("--no-c3", action="store_true", help="skip the config-3 (Repair) timings")
@@ -55,7 +69,8 @@ def parse():
     p.add_argument("--no-roots", action="store_true", help="skip the extension + Merkle roots timing")
     p.add_argument("--no-extras", action="store_true", help="skip host-path and Codec-latency lines")
     p.add_argument("--headline-only", action="store_true",
-                   help="only the headline line (no sub-lines, no CPU baseline): the command the committed "
+                   help="with --full: only the headline line with its oracle gate and isolated-launch timings "
+                        "(no sub-lines, no CPU baseline): the command the committed "
                         "rocprofv3 kernel-trace / PMC summaries are taken from")
     p.add_argument("--dist", action="store_true",
                    help="initialise torch.distributed even at N=1 (rehearses the sharded c5 path on one GPU)")
@@ -73,8 +88,8 @@ def parse():
                    help="GF(2^8) M=128 with >1 stream: CUs of the row-pass persistent grid (0 = all); the "
                         "remaining CUs run the other stream's column pass (profiles/r01h_grid_ab.txt)")
     a = p.parse_args()
-    a.no_single = a.headline_only
-    if a.headline_only:
+    a.no_single = a.headline_only or not a.full
+    if a.headline_only or not a.full:
         a.no_cpu_baseline = a.no_c5 = a.no_c3 = a.no_c4 = a.no_gf16_repair = a.no_roots = a.no_extras = True
     return a
 
@@ -1117,6 +1132,27 @@ def bench_roots(local, L, R, buf, k, S, B, steps):
                     "one launch pair per batch"}
 
 
+def dump_outputs(path, buf, B, W, S, budget=48 * 10**6):
+    """--dump-outputs: what the last timed step left in its EDS buffer `buf` (B squares of
+    W x W shares of S bytes, the squares a caller of rsm_extend_squares_dev gets back), as
+    `path`/eds_sample.npy: float32 [squares, rows, W, S], one value per byte.  The whole
+    batch is 16 GiB, so a fixed sample of at most `budget` bytes of float32 is written:
+    the first and the last square and seeded picks between them, and of each a seeded set
+    of whole rows (Q0|Q1 rows and Q2|Q3 rows alike).  The picks depend on B, W and S only
+    and the ODS are seeded, so two builds run with the same arguments write the same
+    cells."""
+    import numpy as np
+    rs = np.random.default_rng(0xD0)
+    squares = np.unique(np.concatenate([[0, B - 1], rs.choice(B, size=min(B, 6), replace=False)]))
+    nrows = max(1, min(W, budget // 4 // (len(squares) * W * S)))
+    out = np.empty((len(squares), nrows, W, S), np.float32)
+    for i, j in enumerate(squares):
+        for n, r in enumerate(np.sort(rs.choice(W, size=nrows, replace=False))):
+            out[i, n] = buf.download(W * S, (int(j) * W + int(r)) * W * S).reshape(W, S)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "eds_sample.npy"), out)
+
+
 def main():
     a = parse()
     import ctypes
@@ -1214,10 +1250,11 @@ def main():
 
     # the first warmup step, then the correctness gate on its output (the oracle is the
     # checker only), then the remaining warmup steps: the timed steps follow warm steps
-    # directly (a GPU left idle during the CPU-side gate drops its clocks)
+    # directly (a GPU left idle during the CPU-side gate drops its clocks).  The gate is
+    # part of --full; a plain run only warms up.
     step()
     sync_all()
-    if rank == 0:
+    if rank == 0 and a.full:
         import oracle
         for j in sorted({0, B - 1}):  # first and last square of the batch
             got = buf.download(sq_bytes, j * sq_bytes).reshape(W, W, S)
@@ -1246,6 +1283,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, bufs[(nstep[0] - 1) % len(bufs)], B, W, S)
     # per-launch durations of THIS timed run (events on the launch streams)
     rows, cols, spans = [], [], []
     ms = ctypes.c_float()
@@ -1269,12 +1308,14 @@ def main():
     t_row = sum(rows) / len(rows) if rows else 0.0
     t_col = sum(cols) / len(cols) if cols else 0.0
     t_span = sum(spans) / len(spans)
-    # the same launches alone on one stream (no overlap with another step)
+    # the same launches alone on one stream (no overlap with another step): runs of
+    # their own, so --full only
     r_ms, c_ms, s_ms = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-    R._check(L.rsm_time_extend(ctx, bufs[0].ptr, k, S, B, 10, ctypes.byref(r_ms), ctypes.byref(c_ms),
-                               ctypes.byref(s_ms)))
+    if a.full:
+        R._check(L.rsm_time_extend(ctx, bufs[0].ptr, k, S, B, 10, ctypes.byref(r_ms), ctypes.byref(c_ms),
+                                   ctypes.byref(s_ms)))
     iso_single = None
-    if single:
+    if single and a.full:
         e0, e1 = new_event(), new_event()
         R._check(L.rsm_event_record(ctx, e0, None))
         for _ in range(5):
@@ -1364,9 +1405,10 @@ def main():
                                               "p90": us(pct(cols, .9))}}),
                           "step_span_us": {"mean": us(t_span), "p10": us(pct(spans, .1)), "p50": us(pct(spans, .5)),
                                            "p90": us(pct(spans, .9))},
-                          "isolated_one_stream_us": dict(
+                          **({"isolated_one_stream_us": dict(
                               ({"single_launch": us(iso_single)} if single else {}),
-                              two_launch_row=round(r_ms.value * 1e3, 2), two_launch_col=round(c_ms.value * 1e3, 2))},
+                              two_launch_row=round(r_ms.value * 1e3, 2),
+                              two_launch_col=round(c_ms.value * 1e3, 2))} if a.full else {})},
     }
     if rank == 0 and world == 1:
         model, ncpu = cpu_info()

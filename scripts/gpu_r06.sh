@@ -17,10 +17,10 @@ for s in ${STEPS:-smoke tests}; do
     smoke) step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" || exit 3 ;;
     large) step large 900 python3 -u -m pytest tests/test_gpu_large.py -m gpu -v -x --timeout 300 --timeout-method thread || exit 4 ;;
     tests) step pytest_gpu 1000 python3 -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread || exit 5 ;;
-    bench) step bench 700 python3 bench.py || exit 6 ;;
-    headline) step prof 300 rocprofv3 --kernel-trace --stats -d "$PWD/$OUT/prof" -o run --output-format csv -- python3 bench.py --headline-only --steps 50 || exit 7 ;;
-    pmc) step pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -d "$PWD/$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --headline-only --steps 3 --warmup 1 || exit 8
-         step pmc_write 300 rocprofv3 --pmc WRITE_SIZE -d "$PWD/$OUT/pmc_write" -o run --output-format csv -- python3 bench.py --headline-only --steps 3 --warmup 1 || exit 9
+    bench) step bench 700 python3 bench.py --full || exit 6 ;;
+    headline) step prof 300 rocprofv3 --kernel-trace --stats -d "$PWD/$OUT/prof" -o run --output-format csv -- python3 bench.py --full --headline-only --steps 50 || exit 7 ;;
+    pmc) step pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -d "$PWD/$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --full --headline-only --steps 3 --warmup 1 || exit 8
+         step pmc_write 300 rocprofv3 --pmc WRITE_SIZE -d "$PWD/$OUT/pmc_write" -o run --output-format csv -- python3 bench.py --full --headline-only --steps 3 --warmup 1 || exit 9
          python3 scripts/pmc_summary.py $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_latest.json > $OUT/pmc_summary.log 2>&1 ;;
     gf16pmc)  # counters of the production GF(2^16) encoders (c4 k=256 S=2048, c5 k=512 S=512)
          i=0
