@@ -292,6 +292,60 @@ int rsm_nmt_roots_dev(rsm_ctx* ctx, const void* d_eds, uint32_t width, uint32_t 
 int rsm_nmt_roots_squares_dev(rsm_ctx* ctx, const void* d_eds, uint32_t width, uint32_t share_size, uint32_t count,
                               const rsm_nmt_params* params, void* d_roots, void* d_status, void* stream);
 
+/* ---- share inclusion proofs ------------------------------------------------------ */
+/* A share with its Merkle proof against the row or column root: what a node serving
+ * data-availability samples hands out, and the "Merkle proof for each share" a fraud
+ * proof carries (extendeddatacrossword_test.go:19-21).  The tree is selected as in
+ * rsm_eds_roots: nmt == NULL is the DefaultTree, else the erasured NMT.
+ *
+ * The tree over the W leaves of a vector, by levels: node (l, j) covers leaves
+ * [j 2^l, min((j+1) 2^l, W)); level l has ceil(W / 2^l) nodes and an unpaired last
+ * node is carried up unchanged (the RFC 6962 split, the merkletree stack).  The proof
+ * of leaf p lists, for l = 0 .. L-1 (L = ceil(log2 W), 0 for W = 1) and j = p >> l,
+ * node (l, j ^ 1) where j ^ 1 is below the level's node count -- bottom-up, the order
+ * merkletree.Prove() returns after the leaf (datasquare_test.go:514-537).
+ * Node bytes: DefaultTree the 32-byte digest; NMT min || max || digest
+ * (2 * namespace_size + 32), as roots.
+ * Proof record, fixed stride rsm_proof_record_bytes = 8 + L * node_len:
+ *   uint32 n_nodes | uint32 right_mask (bit i: node i is the RIGHT operand of its
+ *   parent hash) | n_nodes nodes, bottom-up | zeros                                  */
+typedef struct {
+    uint32_t square; /* square of a batch */
+    uint32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */
+    uint32_t index;  /* row or column */
+    uint32_t pos;    /* leaf of that vector */
+} rsm_sample;
+/* Bytes of the node store of `count` squares (opaque to callers); 0 for shapes the
+ * device trees do not take (the limits of rsm_roots_dev / rsm_nmt_roots_dev). */
+uint64_t rsm_proof_nodes_bytes(uint32_t width, const rsm_nmt_params* nmt, uint32_t count);
+/* Bytes of one proof record (any width >= 1; 0 for width 0 or a namespace size 0). */
+uint32_t rsm_proof_record_bytes(uint32_t width, const rsm_nmt_params* nmt);
+/* Builds the node store of `count` consecutive complete device squares: every node of
+ * their 2 * width trees, into d_nodes (device, rsm_proof_nodes_bytes, 16-byte aligned;
+ * no other scratch).  d_roots / d_status (device, nullable) receive what
+ * rsm_roots_squares_dev / rsm_nmt_roots_squares_dev write (DefaultTree statuses: 0).
+ * RSM_EUNSUPPORTED beyond those calls' limits.  Asynchronous on `stream`. */
+int rsm_proof_nodes_dev(rsm_ctx* ctx, const void* d_eds, uint32_t width, uint32_t share_size, uint32_t count,
+                        const rsm_nmt_params* nmt, void* d_nodes, void* d_roots, void* d_status, void* stream);
+/* n proof records out of a node store: d_records (device) receives n records;
+ * d_shares (device, nullable, 16-byte aligned; needs d_eds, the squares the store was
+ * built from) the n sampled shares, [n][share_size].  `samples` is HOST memory,
+ * validated before anything is enqueued (RSM_EINVAL names the first sample with
+ * square >= count, axis > 1, index >= width or pos >= width) and copied before the call
+ * returns.  The records are written asynchronously on `stream`. */
+int rsm_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_t width, uint32_t share_size,
+                   uint32_t count, const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n, void* d_records,
+                   void* d_shares, void* stream);
+/* Host restatements (merkle.cpp), any n_leaves >= 1: the proof record of leaf `pos`
+ * into record_out (rsm_proof_record_bytes(n_leaves, ..)) and the root into root_out
+ * (nullable; 32 / 2 * namespace_size + 32 bytes).  The NMT form applies the wrapper's
+ * rules as rsm_nmt_tree_root does (`index` decides quadrant 0; RSM_ETREE on push
+ * order, sibling order, a vector past the square, data shorter than a namespace). */
+int rsm_default_tree_prove(const uint8_t* const* leaves, uint32_t n_leaves, uint32_t leaf_size, uint32_t pos,
+                           uint8_t* record_out, uint8_t* root_out);
+int rsm_nmt_tree_prove(const rsm_nmt_params* params, uint32_t index, const uint8_t* const* leaves, uint32_t n_leaves,
+                       uint32_t leaf_size, uint32_t pos, uint8_t* record_out, uint8_t* root_out);
+
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */
 int rsm_eds_compute(rsm_ctx* ctx, const uint8_t* const* data, const uint32_t* lens, uint64_t n,
@@ -320,6 +374,19 @@ int rsm_eds_flattened(const rsm_eds* eds, uint8_t* out, uint8_t* present);
 /* RowRoots()/ColRoots() (:258-280): width roots of root_cap bytes each. */
 int rsm_eds_roots(rsm_eds* eds, int axis, rsm_tree_root_fn tree_fn, void* user, uint8_t* roots_out,
                   uint32_t root_cap, uint32_t* root_len);
+
+/* Proofs of n samples (square = 0) of this square: n records of
+ * rsm_proof_record_bytes(width, nmt) into records_out, the n shares into shares_out
+ * (nullable).  tree_fn / user as rsm_eds_roots (NULL or rsm_default_tree_root: the
+ * DefaultTree; rsm_nmt_tree_root with its params: the NMT); any other plugin
+ * RSM_EUNSUPPORTED.  RSM_EINVAL for a sample out of range; RSM_ETREE for a sample in
+ * an incomplete vector or in a tree that fails.  With a context and a complete square
+ * of a width the device trees take, the node store is built once on the GPU and kept
+ * with the square (dropped by SetCell, Repair and rsm_eds_set_context); later calls
+ * only gather.  Otherwise the host restatement runs per sample.  Results never depend
+ * on the path. */
+int rsm_eds_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
+                   uint8_t* records_out, uint8_t* shares_out);
 
 typedef struct {
     int32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */

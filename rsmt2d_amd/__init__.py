@@ -33,7 +33,7 @@ __all__ = [
     "ErasuredNamespacedMerkleTreeConstructor", "newErasuredNamespacedMerkleTreeConstructor",
     "TreePool", "newTreePool",
     "ErrUnrepairableDataSquare", "ErrUnevenChunks", "RSMError", "DeviceError",
-    "library", "build", "device_context",
+    "library", "build", "device_context", "Proof", "Sample", "prove_samples_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -188,6 +188,13 @@ SIGNATURES = {
     "rsm_eds_repair": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, ctypes.POINTER(_Byz)]),
     "rsm_eds_byzantine_shares": (_I32, [_VP, _VP, _VP]),
     "rsm_eds_repair_stats": (_I32, [_VP, ctypes.POINTER(RepairStats)]),
+    "rsm_proof_nodes_bytes": (_U64, [_U32, ctypes.POINTER(NmtParams), _U32]),
+    "rsm_proof_record_bytes": (_U32, [_U32, ctypes.POINTER(NmtParams)]),
+    "rsm_proof_nodes_dev": (_I32, [_VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP, _VP, _VP]),
+    "rsm_proofs_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _U32, _VP, _VP, _VP]),
+    "rsm_default_tree_prove": (_I32, [_VP, _U32, _U32, _U32, _VP, _VP]),
+    "rsm_nmt_tree_prove": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _U32, _VP, _VP]),
+    "rsm_eds_proofs": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP]),
 }
 
 
@@ -578,6 +585,102 @@ def _default_root(leaves: Sequence[bytes]) -> bytes:
 
 
 # ---------------------------------------------------------------------------
+# Share inclusion proofs (include/rsmt2d_hip.h "share inclusion proofs")
+# ---------------------------------------------------------------------------
+class Sample(ctypes.Structure):
+    """rsm_sample: leaf ``pos`` of row (axis 0) / column (axis 1) ``index`` of ``square``."""
+    _fields_ = [("square", ctypes.c_uint32), ("axis", ctypes.c_uint32), ("index", ctypes.c_uint32),
+                ("pos", ctypes.c_uint32)]
+
+
+class Proof:
+    """A share with its Merkle proof in a row or column tree.
+
+    ``share``: the leaf; ``nodes``: the siblings bottom-up (32-byte digests for the
+    DefaultTree, min || max || digest for the NMT); ``right_mask``: bit i set when
+    ``nodes[i]`` is the right operand of its parent hash; ``index``: the leaf's
+    position; ``numLeaves``: the tree's leaf count; ``root``: the root the proof folds
+    to (compare it with the committed row / column root).  ``nmt``: the tree's
+    NmtParams, None for the DefaultTree; ``tree_index``: the row / column."""
+
+    def __init__(self, share: bytes, nodes: List[bytes], right_mask: int, index: int, numLeaves: int,
+                 nmt: Optional[NmtParams] = None, tree_index: int = 0):
+        self.share, self.nodes, self.right_mask = share, nodes, right_mask
+        self.index, self.numLeaves, self.nmt, self.tree_index = index, numLeaves, nmt, tree_index
+
+    def proofSet(self) -> List[bytes]:
+        """``[share] + nodes``: the proofSet of merkletree.Prove() (treeProve,
+        datasquare_test.go:514-537)."""
+        return [self.share] + list(self.nodes)
+
+    def nmt_nodes(self) -> List[bytes]:
+        """The same nodes in the order of nmt's ``Proof.Nodes`` for the range
+        [index, index + 1): an in-order walk -- the left-hand siblings from the top
+        down, then the right-hand ones from the bottom up.  The nmt library is not
+        available to this project's tests, so parity with it is unpinned, as it is for
+        the NMT roots."""
+        left = [nd for i, nd in enumerate(self.nodes) if not (self.right_mask >> i) & 1]
+        right = [nd for i, nd in enumerate(self.nodes) if (self.right_mask >> i) & 1]
+        return left[::-1] + right
+
+    @property
+    def root(self) -> bytes:
+        import hashlib
+        if self.nmt is None:
+            acc = hashlib.sha256(b"\x00" + self.share).digest()
+            for i, nd in enumerate(self.nodes):
+                l, r = (acc, nd) if (self.right_mask >> i) & 1 else (nd, acc)
+                acc = hashlib.sha256(b"\x01" + l + r).digest()
+            return acc
+        ns, k = int(self.nmt.namespace_size), int(self.nmt.square_size)
+        nid = self.share[:ns] if (self.index < k and self.tree_index < k) else b"\xff" * ns
+        acc = nid + nid + hashlib.sha256(b"\x00" + nid + self.share).digest()
+        for i, nd in enumerate(self.nodes):
+            l, r = (acc, nd) if (self.right_mask >> i) & 1 else (nd, acc)
+            mx = l[ns:2 * ns] if (self.nmt.ignore_max_namespace and r[:ns] == b"\xff" * ns) else r[ns:2 * ns]
+            acc = l[:ns] + mx + hashlib.sha256(b"\x01" + l + r).digest()
+        return acc
+
+
+def _parse_records(rec: bytes, shares: bytes, samples, width: int, S: int, nmt: Optional[NmtParams]) -> List[Proof]:
+    """Proof objects from n proof records and the n shares; samples: (axis, index, pos)."""
+    nl = 32 if nmt is None else 2 * int(nmt.namespace_size) + 32
+    levels = (width - 1).bit_length()
+    rb = 8 + levels * nl
+    out = []
+    for i, (_axis, index, pos) in enumerate(samples):
+        r = rec[i * rb:(i + 1) * rb]
+        n_nodes, mask = int.from_bytes(r[0:4], "little"), int.from_bytes(r[4:8], "little")
+        nodes = [r[8 + j * nl: 8 + (j + 1) * nl] for j in range(n_nodes)]
+        out.append(Proof(shares[i * S:(i + 1) * S], nodes, mask, pos, width, nmt, index))
+    return out
+
+
+def prove_samples_dev(buf: "DeviceBuffer", width: int, share_size: int, samples: Sequence[tuple],
+                      nmt: Optional[NmtParams] = None, count: int = 1) -> List[Proof]:
+    """Proofs of ``(square, axis, index, pos)`` samples of ``count`` complete
+    device-resident [width][width][share_size] squares in ``buf``: one node-store
+    build (rsm_proof_nodes_dev), one gather (rsm_proofs_dev)."""
+    L, ctx, n = library(), buf.ctx, len(samples)
+    p = ctypes.byref(nmt) if nmt is not None else None
+    nbytes = int(L.rsm_proof_nodes_bytes(width, p, count))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device proofs: {count} squares of width {width} not supported")
+    rb = int(L.rsm_proof_record_bytes(width, p))
+    nodes, recs, shs = DeviceBuffer(nbytes), DeviceBuffer(max(n * rb, 16)), DeviceBuffer(max(n * share_size, 16))
+    try:
+        arr = (Sample * max(n, 1))(*[Sample(*s) for s in samples])
+        _check(L.rsm_proof_nodes_dev(ctx, buf.ptr, width, share_size, count, p, nodes.ptr, None, None, None))
+        _check(L.rsm_proofs_dev(ctx, nodes.ptr, buf.ptr, width, share_size, count, p, arr, n, recs.ptr, shs.ptr, None))
+        _check(L.rsm_sync(ctx))
+        rec, sh = recs.download(max(n * rb, 16)).tobytes(), shs.download(max(n * share_size, 16)).tobytes()
+    finally:
+        for b in (nodes, recs, shs):
+            b.free()
+    return _parse_records(rec, sh, [s[1:] for s in samples], width, share_size, nmt)
+
+
+# ---------------------------------------------------------------------------
 # ExtendedDataSquare (extendeddatasquare.go)
 # ---------------------------------------------------------------------------
 class ExtendedDataSquare:
@@ -691,6 +794,36 @@ class ExtendedDataSquare:
             raw, p = out.raw, pres.raw
             raise ErrByzantineData(byz.axis, byz.index, [raw[i * S:(i + 1) * S] if p[i] else None for i in range(w)])
         raise _err(rc)
+
+    # --- share inclusion proofs (rsm_eds_proofs) ---
+    def Proofs(self, samples: Sequence[tuple]) -> List["Proof"]:
+        """Proofs of ``(axis, index, pos)`` samples (leaf ``pos`` of row / column
+        ``index``) against this square's row / column roots, with the tree of the
+        square's constructor (NewDefaultTree, the erasured NMT constructor or the
+        pool's); other Tree plugins raise RSM_EUNSUPPORTED.  A complete square with a
+        device context builds its tree nodes on the GPU once and keeps them until a
+        cell changes; anything else runs the host trees."""
+        tf = self._tree_fn
+        if not (tf is None or tf is NewDefaultTree or isinstance(tf, ErasuredNamespacedMerkleTreeConstructor)):
+            raise RSMError(RSM_EUNSUPPORTED, "proofs are built for the DefaultTree and the NMT only")
+        keep, fn, user = _tree_callback(tf)
+        nmt = tf.params if isinstance(tf, ErasuredNamespacedMerkleTreeConstructor) else None
+        L, w, S, n = library(), self.Width(), self.shareSize, len(samples)
+        arr = (Sample * max(n, 1))(*[Sample(0, a, i, p) for (a, i, p) in samples])
+        rb = int(L.rsm_proof_record_bytes(max(w, 1), ctypes.byref(nmt) if nmt is not None else None))
+        rec = ctypes.create_string_buffer(max(n * rb, 1))
+        sh = ctypes.create_string_buffer(max(n * S, 1))
+        _check(L.rsm_eds_proofs(self._h, fn, user, arr, n, rec, sh))
+        return _parse_records(rec.raw, sh.raw, samples, w, S, nmt)
+
+    def RowProof(self, rowIdx: int, colIdx: int) -> "Proof":
+        """Share (rowIdx, colIdx) with its proof against RowRoots()[rowIdx]
+        (computeRowProof, datasquare_test.go:514-537)."""
+        return self.Proofs([(Row, rowIdx, colIdx)])[0]
+
+    def ColProof(self, rowIdx: int, colIdx: int) -> "Proof":
+        """Share (rowIdx, colIdx) with its proof against ColRoots()[colIdx]."""
+        return self.Proofs([(Col, colIdx, rowIdx)])[0]
 
     def repair_stats(self) -> RepairStats:
         st = RepairStats()

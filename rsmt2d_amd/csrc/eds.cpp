@@ -11,7 +11,7 @@
 //     failure of that path (unrepairable, byzantine) falls back to the exact
 //     sequential reference order (solveCrossword, :87-282) using the
 //     per-codeword device codec, so error identity matches the reference.
-#include "rsm_internal.hpp"
+#include "eds_internal.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -22,71 +22,6 @@
 #include <vector>
 
 using namespace rsm;
-
-// Host bytes of a square: pinned (hipHostMalloc) whenever a HIP runtime is
-// usable, so Repair's square upload and download are direct DMA; plain memory on
-// a host without a GPU (Import/New are host-only operations).
-struct HostSquare {
-    uint8_t* p = nullptr;
-    size_t n = 0;
-    bool pinned = false;
-    HostSquare() = default;
-    HostSquare(const HostSquare&) = delete;
-    HostSquare& operator=(const HostSquare&) = delete;
-    ~HostSquare() { release(); }
-    void release() {
-        if (p) {
-            if (pinned) (void)hipHostFree(p);
-            else free(p);
-        }
-        p = nullptr;
-        n = 0;
-    }
-    bool assign(size_t bytes) {  // zero-filled
-        release();
-        if (bytes == 0) return true;
-        void* q = nullptr;
-        if (hipHostMalloc(&q, bytes, hipHostMallocDefault) == hipSuccess) {
-            pinned = true;
-        } else {
-            (void)hipGetLastError();
-            q = malloc(bytes);
-            pinned = false;
-            if (!q) return false;
-        }
-        p = static_cast<uint8_t*>(q);
-        n = bytes;
-        memset(p, 0, n);
-        return true;
-    }
-    uint8_t* data() { return p; }
-    const uint8_t* data() const { return p; }
-    size_t size() const { return n; }
-    void swap(HostSquare& o) {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        std::swap(pinned, o.pinned);
-    }
-};
-
-struct rsm_eds {
-    rsm_ctx* ctx = nullptr;
-    uint32_t width = 0;
-    uint32_t odw = 0;  // originalDataWidth
-    uint32_t S = 0;    // shareSize
-    HostSquare data;               // width*width*S, row-major
-    std::vector<uint8_t> present;  // width*width
-    std::vector<uint8_t> byz_data;
-    std::vector<uint8_t> byz_present;
-    rsm_repair_stats stats{};
-
-    uint8_t* cell(uint32_t r, uint32_t c) { return data.data() + ((size_t)r * width + c) * S; }
-    const uint8_t* cell(uint32_t r, uint32_t c) const { return data.data() + ((size_t)r * width + c) * S; }
-    bool has(uint32_t r, uint32_t c) const { return present[(size_t)r * width + c] != 0; }
-    // (axis, index, position) -> cell coordinates
-    uint32_t rr(int axis, uint32_t idx, uint32_t pos) const { return axis == RSM_AXIS_ROW ? idx : pos; }
-    uint32_t cc(int axis, uint32_t idx, uint32_t pos) const { return axis == RSM_AXIS_ROW ? pos : idx; }
-};
 
 // Repair A/B (diagnostic builds): 1 = the zero-copy sweep as two launches, top half then
 // bottom half, the column re-encode of the top half overlapping the bottom sweep (the
@@ -931,6 +866,7 @@ void rsm_eds_free(rsm_eds* eds) { delete eds; }
 // Attach (or replace) the GPU context of a square built host-only.
 int rsm_eds_set_context(rsm_eds* e, rsm_ctx* ctx) {
     if (!e) return fail(RSM_EINVAL, "NULL eds");
+    e->proofs.drop();  // a node store lives on the context it was built on
     e->ctx = ctx;
     return RSM_OK;
 }
@@ -950,6 +886,7 @@ int rsm_eds_set_cell(rsm_eds* e, uint32_t row, uint32_t col, const uint8_t* shar
     if (e->has(row, col)) return fail(RSM_ECELL, "cannot set cell (%u, %u) as it already has a value", row, col);
     if (!share || len != e->S)
         return fail(RSM_ECELL, "cannot set cell with chunk size %u because dataSquare chunk size is %u", len, e->S);
+    e->proofs.drop();  // as resetRoots: the cached tree nodes no longer match
     memcpy(e->cell(row, col), share, e->S);
     e->present[(size_t)row * e->width + col] = 1;
     return RSM_OK;
@@ -957,6 +894,7 @@ int rsm_eds_set_cell(rsm_eds* e, uint32_t row, uint32_t col, const uint8_t* shar
 
 int rsm_eds_overwrite_cell(rsm_eds* e, uint32_t row, uint32_t col, const uint8_t* share, uint32_t len) {
     if (!e || row >= e->width || col >= e->width) return fail(RSM_EINVAL, "setCell: index out of range");
+    e->proofs.drop();
     if (!share) {
         e->present[(size_t)row * e->width + col] = 0;
         memset(e->cell(row, col), 0, e->S);
@@ -1042,6 +980,7 @@ int rsm_eds_repair(rsm_eds* e, const uint8_t* row_roots, const uint8_t* col_root
                    rsm_tree_root_fn tree_fn, void* user, rsm_byzantine* byz) {
     if (!e || !row_roots || !col_roots || root_len == 0) return fail(RSM_EINVAL, "Repair: bad arguments");
     e->stats = rsm_repair_stats{};
+    e->proofs.drop();
     e->byz_data.clear();
     e->byz_present.clear();
     if (byz) {

@@ -1,0 +1,98 @@
+// eds_internal.hpp -- the ExtendedDataSquare object, shared by eds.cpp and rsm_proof.cpp.
+#pragma once
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "rsm_internal.hpp"
+
+// Host bytes of a square: pinned (hipHostMalloc) whenever a HIP runtime is
+// usable, so Repair's square upload and download are direct DMA; plain memory on
+// a host without a GPU (Import/New are host-only operations).
+struct HostSquare {
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    bool pinned = false;
+    HostSquare() = default;
+    HostSquare(const HostSquare&) = delete;
+    HostSquare& operator=(const HostSquare&) = delete;
+    ~HostSquare() { release(); }
+    void release() {
+        if (p) {
+            if (pinned) (void)hipHostFree(p);
+            else free(p);
+        }
+        p = nullptr;
+        n = 0;
+    }
+    bool assign(size_t bytes) {  // zero-filled
+        release();
+        if (bytes == 0) return true;
+        void* q = nullptr;
+        if (hipHostMalloc(&q, bytes, hipHostMallocDefault) == hipSuccess) {
+            pinned = true;
+        } else {
+            (void)hipGetLastError();
+            q = malloc(bytes);
+            pinned = false;
+            if (!q) return false;
+        }
+        p = static_cast<uint8_t*>(q);
+        n = bytes;
+        memset(p, 0, n);
+        return true;
+    }
+    uint8_t* data() { return p; }
+    const uint8_t* data() const { return p; }
+    size_t size() const { return n; }
+    void swap(HostSquare& o) {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        std::swap(pinned, o.pinned);
+    }
+};
+
+// The node store of a complete square (rsm_eds_proofs' device path): built once for one
+// tree, kept until a cell, the context or the tree changes (the reference's resetRoots
+// on SetCell is the pattern).  Its own device allocation, on the context it was built on.
+struct ProofStore {
+    void* d_nodes = nullptr;
+    rsm_ctx* ctx = nullptr;
+    bool nmt = false;
+    rsm_nmt_params p{};
+    std::vector<uint32_t> status;  // 2 * width words: non-zero where a tree fails
+    ProofStore() = default;
+    ProofStore(const ProofStore&) = delete;
+    ProofStore& operator=(const ProofStore&) = delete;
+    ~ProofStore() { drop(); }
+    void drop() {
+        if (d_nodes) {
+            if (ctx) (void)hipSetDevice(ctx->device);
+            (void)hipFree(d_nodes);
+        }
+        d_nodes = nullptr;
+        ctx = nullptr;
+        status.clear();
+    }
+};
+
+struct rsm_eds {
+    rsm_ctx* ctx = nullptr;
+    uint32_t width = 0;
+    uint32_t odw = 0;  // originalDataWidth
+    uint32_t S = 0;    // shareSize
+    HostSquare data;               // width*width*S, row-major
+    std::vector<uint8_t> present;  // width*width
+    std::vector<uint8_t> byz_data;
+    std::vector<uint8_t> byz_present;
+    rsm_repair_stats stats{};
+    ProofStore proofs;
+
+    uint8_t* cell(uint32_t r, uint32_t c) { return data.data() + ((size_t)r * width + c) * S; }
+    const uint8_t* cell(uint32_t r, uint32_t c) const { return data.data() + ((size_t)r * width + c) * S; }
+    bool has(uint32_t r, uint32_t c) const { return present[(size_t)r * width + c] != 0; }
+    // (axis, index, position) -> cell coordinates
+    uint32_t rr(int axis, uint32_t idx, uint32_t pos) const { return axis == RSM_AXIS_ROW ? idx : pos; }
+    uint32_t cc(int axis, uint32_t idx, uint32_t pos) const { return axis == RSM_AXIS_ROW ? pos : idx; }
+};

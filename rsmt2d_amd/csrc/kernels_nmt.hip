@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <utility>
 
+#include "rsm_kernels.hpp"
 #include "sha256_dev.hpp"
 
 namespace rsm {
@@ -699,7 +700,145 @@ hipError_t launch_nmt_tree_wave(const uint32_t* d_leaf, uint32_t W, uint32_t ign
     return hipGetLastError();
 }
 
+// Node-store build (share inclusion proofs, rsm_kernels.hpp "proof_*"): the trees above
+// by levels, every node of levels 1 .. L written to the store by the lane that hashed
+// it (six 16-byte stores: min[8] | max[8] | digest[8] words), an unpaired last node
+// carried up as a copy.  One workgroup builds `tpb` <= 32 trees together (first tree
+// blockIdx.x * tpb, square blockIdx.y): node j of tree u of a level is slot u * cnt + j,
+// the level in place in the tree's LDS (ceil(W / 2) nodes; a barrier between a pass's
+// reads and its writes).  NS = 29: the register-assembled node message of the wave
+// kernel; NS = 0: any namespace size, the message in the lane's LDS bytes.  Checks,
+// roots and statuses as nmt_tree_kernel.
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_nodes_kernel(uint32_t* __restrict__ store, uint32_t W, uint32_t ns,
+                                                        uint32_t ignore_max, uint32_t tpb, uint8_t* __restrict__ roots,
+                                                        uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];
+    __shared__ uint32_t wg_bad;  // bit u: workgroup tree u failed
+    if (threadIdx.x == 0) wg_bad = 0;
+    const uint32_t half = (W + 1) / 2, L = proof_levels(W), U = proof_tree_nodes(W);
+    const uint32_t tw0 = blockIdx.x * tpb;
+    const uint32_t ntw = 2 * W - tw0 < tpb ? 2 * W - tw0 : tpb;
+    const uint32_t* leaf = store + (uint64_t)blockIdx.y * W * W * kLeafWords;
+    uint32_t* upper = store + (uint64_t)gridDim.y * W * W * kLeafWords +
+                      ((uint64_t)blockIdx.y * 2 * W + tw0) * U * kNodeWords;
+    uint8_t* mb = reinterpret_cast<uint8_t*>(lds + (size_t)tpb * half * kNodeWords) +
+                  (NS == 0 ? threadIdx.x * (64u * node_blocks(ns)) : 0u);
+    const bool ig = ignore_max != 0;
+    auto cell_of = [&](uint32_t tree, uint32_t pos) -> uint64_t {
+        const uint32_t axis = tree >= W ? 1u : 0u, idx = tree - axis * W;
+        return axis == 0 ? (uint64_t)idx * W + pos : (uint64_t)pos * W + idx;
+    };
+    auto hash = [&](const Node& a, const Node& b, Node& o) -> bool {
+        if constexpr (NS == 0) {
+            return hash_node(a, b, ns, ig, mb, o);
+        } else {
+            static_assert(WNode<NS>::kW == (int)kNsWords, "a WNode laid out as a Node");
+            WNode<NS> x, y, z;
+#pragma unroll
+            for (int i = 0; i < (int)kNsWords; ++i) x.mn[i] = a.mn[i], x.mx[i] = a.mx[i], y.mn[i] = b.mn[i], y.mx[i] = b.mx[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) x.d[i] = a.d[i], y.d[i] = b.d[i];
+            const bool ok = hash_node_w<NS>(x, y, ig, z);
+#pragma unroll
+            for (int i = 0; i < (int)kNsWords; ++i) o.mn[i] = z.mn[i], o.mx[i] = z.mx[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o.d[i] = z.d[i];
+            return ok;
+        }
+    };
+    __syncthreads();  // wg_bad zeroed before any atomicOr
+    uint32_t prev = W, off = 0;  // nodes of level l - 1; level l's first node in a tree's block
+    for (uint32_t l = 1; l <= L; ++l) {
+        const uint32_t cnt = (prev + 1) / 2, tot = ntw * cnt;
+        for (uint32_t v0 = 0; v0 < tot; v0 += 256u) {
+            const uint32_t v = v0 + threadIdx.x;
+            const bool act = v < tot;
+            const uint32_t u = act ? v / cnt : 0u, j = act ? v - u * cnt : 0u;
+            Node o;
+            if (act) {
+                Node a, b;
+                bool ok = true;
+                const bool pair = 2 * j + 1 < prev;
+                if (l == 1) {  // from the leaf records; push order on every consecutive pair
+                    leaf_node(leaf, cell_of(tw0 + u, 2 * j), a);
+                    if (pair) {
+                        leaf_node(leaf, cell_of(tw0 + u, 2 * j + 1), b);
+                        if (ns_less(b.mn, a.mn)) ok = false;
+                        if (2 * j + 2 < prev) {
+                            Node c;
+                            leaf_node(leaf, cell_of(tw0 + u, 2 * j + 2), c);
+                            if (ns_less(c.mn, b.mn)) ok = false;
+                        }
+                    }
+                } else {
+                    const uint32_t* lv = lds + (size_t)u * half * kNodeWords;
+                    lds_node(lv + (size_t)(2 * j) * kNodeWords, a);
+                    if (pair) lds_node(lv + (size_t)(2 * j + 1) * kNodeWords, b);
+                }
+                if (pair) {
+                    if (!hash(a, b, o)) ok = false;
+                } else {
+                    o = a;  // carried up unchanged
+                }
+                if (!ok) atomicOr(&wg_bad, 1u << u);
+            }
+            __syncthreads();  // every read of this pass precedes its in-place writes
+            if (act) {
+                lds_store(lds + ((size_t)u * half + j) * kNodeWords, o);
+                nv4u* g = reinterpret_cast<nv4u*>(upper + ((uint64_t)u * U + off + j) * kNodeWords);
+                g[0] = nv4u{o.mn[0], o.mn[1], o.mn[2], o.mn[3]};
+                g[1] = nv4u{o.mn[4], o.mn[5], o.mn[6], o.mn[7]};
+                g[2] = nv4u{o.mx[0], o.mx[1], o.mx[2], o.mx[3]};
+                g[3] = nv4u{o.mx[4], o.mx[5], o.mx[6], o.mx[7]};
+                g[4] = nv4u{o.d[0], o.d[1], o.d[2], o.d[3]};
+                g[5] = nv4u{o.d[4], o.d[5], o.d[6], o.d[7]};
+                if (l == L && roots) {  // cnt == 1: the root, as nmt_tree_kernel lays it out
+                    uint8_t* r = roots + ((uint64_t)blockIdx.y * 2 * W + tw0 + u) * (2 * ns + 32);
+#pragma unroll
+                    for (int i = 0; i < (int)kMaxNs; ++i)
+                        if (i < (int)ns) {
+                            r[i] = be_byte(o.mn, i);
+                            r[ns + i] = be_byte(o.mx, i);
+                        }
+#pragma unroll
+                    for (int i = 0; i < 32; ++i) r[2 * ns + i] = be_byte(o.d, i);
+                }
+            }
+            __syncthreads();
+        }
+        off += cnt;
+        prev = cnt;
+    }
+    // (the last pass's barrier orders every atomicOr before this read)
+    if (status && threadIdx.x < ntw)
+        status[(uint64_t)blockIdx.y * 2 * W + tw0 + threadIdx.x] = (wg_bad >> threadIdx.x) & 1u;
+}
+
 }  // namespace
+
+hipError_t launch_nmt_nodes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+                            uint32_t squares, uint32_t* d_store, uint8_t* d_roots, uint32_t* d_status, hipStream_t st) {
+    if (squares == 0) return hipSuccess;
+    const uint32_t cells = W * W;
+    // the leaf records are the store's level 0 (the leaf kernels as launch_nmt_roots picks them)
+    if (ns == 29 && S % 64 == 0 && S >= 64 && (reinterpret_cast<uintptr_t>(d_eds) & 15u) == 0)
+        hipLaunchKernelGGL(nmt_leaf29_kernel, dim3((cells + 255) / 256, squares), dim3(256), 0, st, d_eds, W, S, k, d_store);
+    else
+        hipLaunchKernelGGL(nmt_leaf_kernel, dim3((cells + 255) / 256, squares), dim3(256), 0, st, d_eds, W, S, ns, k, d_store);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t tpb = proof_trees_per_block(W);
+    const dim3 grid((2 * W + tpb - 1) / tpb, squares);
+    const size_t levels = (size_t)tpb * ((W + 1) / 2) * kNodeWords * 4u;
+    if (ns == 29)
+        hipLaunchKernelGGL(nmt_nodes_kernel<29>, grid, dim3(256), levels, st, d_store, W, ns, ignore_max, tpb, d_roots,
+                           d_status);
+    else
+        hipLaunchKernelGGL(nmt_nodes_kernel<0>, grid, dim3(256), levels + (size_t)256 * 64u * node_blocks(ns), st, d_store,
+                           W, ns, ignore_max, tpb, d_roots, d_status);
+    return hipGetLastError();
+}
 
 bool nmt_dev_supported(uint32_t W, uint32_t ns) {
     return W >= 2 && W <= kMaxWidth && ns >= 1 && ns <= kMaxNs && tree_lds_bytes(W, ns) <= kLdsCap;

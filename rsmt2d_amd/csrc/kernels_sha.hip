@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "rsm_kernels.hpp"
 #include "sha256_dev.hpp"
 
 namespace rsm {
@@ -276,7 +277,103 @@ hipError_t launch_tree_kernel(const uint32_t* d_leaf, uint32_t W, uint8_t* d_roo
     return hipGetLastError();
 }
 
+// Node-store build (share inclusion proofs, rsm_kernels.hpp "proof_*"): the same trees
+// by levels -- node (l, j) over leaves [j 2^l, min((j + 1) 2^l, W)), an unpaired last
+// node carried up unchanged -- with every node of levels 1 .. L written to the store as
+// it is produced (the level picture and the stack of subtrees above give the same
+// tree: a carried node is the right-hand subtree waiting for its fold).  One
+// workgroup builds `tpb` trees (first tree blockIdx.x * tpb, square blockIdx.y)
+// together: node j of tree u of a level is slot u * cnt + j of the workgroup, the
+// level in place in the tree's LDS (ceil(W / 2) nodes; node j reads 2j and 2j + 1 >= j,
+// a barrier between a pass's reads and its writes), and the lane that hashed a node
+// also stores it: two 16-byte stores, consecutive lanes to consecutive nodes.
+__global__ __launch_bounds__(256) void tree_nodes_kernel(uint32_t* __restrict__ store, uint32_t W, uint32_t tpb,
+                                                         uint8_t* __restrict__ roots) {
+    extern __shared__ uint32_t lds_raw[];
+    const uint32_t half = (W + 1) / 2, L = proof_levels(W), U = proof_tree_nodes(W);
+    const uint32_t tw0 = blockIdx.x * tpb;
+    const uint32_t ntw = 2 * W - tw0 < tpb ? 2 * W - tw0 : tpb;
+    const uint32_t* leaf = store + (uint64_t)blockIdx.y * W * W * 8u;
+    uint32_t* upper = store + (uint64_t)gridDim.y * W * W * 8u + ((uint64_t)blockIdx.y * 2 * W + tw0) * U * 8u;
+    auto leaf_at = [&](uint32_t tree, uint32_t pos, uint32_t (&d)[8]) {
+        const uint32_t axis = tree >= W ? 1u : 0u, idx = tree - axis * W;
+        const uint64_t cell = axis == 0 ? (uint64_t)idx * W + pos : (uint64_t)pos * W + idx;
+        const v4u* s = reinterpret_cast<const v4u*>(leaf + cell * 8u);
+        const v4u a = s[0], b = s[1];
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+    };
+    uint32_t prev = W, off = 0;  // nodes of level l - 1; level l's first node in a tree's block
+    for (uint32_t l = 1; l <= L; ++l) {
+        const uint32_t cnt = (prev + 1) / 2, tot = ntw * cnt;
+        for (uint32_t v0 = 0; v0 < tot; v0 += 256u) {
+            const uint32_t v = v0 + threadIdx.x;
+            const bool act = v < tot;
+            const uint32_t u = act ? v / cnt : 0u, j = act ? v - u * cnt : 0u;
+            uint32_t o[8];
+            if (act) {
+                uint32_t a[8], b[8];
+                const bool pair = 2 * j + 1 < prev;
+                if (l == 1) {
+                    leaf_at(tw0 + u, 2 * j, a);
+                    if (pair) leaf_at(tw0 + u, 2 * j + 1, b);
+                } else {
+                    const uint32_t* lv = lds_raw + (size_t)u * half * 8u;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        a[i] = lv[(2 * j) * 8u + i];
+                        b[i] = pair ? lv[(2 * j + 1) * 8u + i] : 0u;
+                    }
+                }
+                if (pair) {
+                    node_hash(a, b, o);
+                } else {  // carried up unchanged
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) o[i] = a[i];
+                }
+            }
+            __syncthreads();  // every read of this pass precedes its in-place writes
+            if (act) {
+                uint32_t* lv = lds_raw + ((size_t)u * half + j) * 8u;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) lv[i] = o[i];
+                v4u* g = reinterpret_cast<v4u*>(upper + ((uint64_t)u * U + off + j) * 8u);
+                g[0] = v4u{o[0], o[1], o[2], o[3]};
+                g[1] = v4u{o[4], o[5], o[6], o[7]};
+                if (l == L && roots) {  // cnt == 1: the root, as tree_root_kernel lays it out
+                    uint32_t* r = reinterpret_cast<uint32_t*>(roots + ((uint64_t)blockIdx.y * 2 * W + tw0 + u) * 32u);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) r[i] = __builtin_bswap32(o[i]);
+                }
+            }
+            __syncthreads();
+        }
+        off += cnt;
+        prev = cnt;
+    }
+}
+
 }  // namespace
+
+// Trees a workgroup of the node-store builds takes: as many as fill its 256 lanes at
+// level 1 (at most 32: the NMT build keeps one failure bit per tree in a word).
+uint32_t proof_trees_per_block(uint32_t W) {
+    const uint32_t half = (W + 1) / 2;
+    const uint32_t t = 256u / half;
+    return t < 1u ? 1u : (t > 32u ? 32u : t);
+}
+
+hipError_t launch_tree_nodes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t squares, uint32_t* d_store,
+                             uint8_t* d_roots, hipStream_t st) {
+    const uint32_t cells = W * W * squares;
+    hipLaunchKernelGGL(leaf_hash_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, d_eds, cells, S, d_store);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t tpb = proof_trees_per_block(W);
+    const size_t lds = (size_t)tpb * ((W + 1) / 2) * 8u * 4u;
+    hipLaunchKernelGGL(tree_nodes_kernel, dim3((2 * W + tpb - 1) / tpb, squares), dim3(256), lds, st, d_store, W, tpb,
+                       d_roots);
+    return hipGetLastError();
+}
 
 bool roots_dev_supported(uint32_t W) { return W >= 2 && W <= 2 * kMaxLevel1 && W < (1u << 16); }
 

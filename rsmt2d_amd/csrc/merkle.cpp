@@ -411,3 +411,128 @@ extern "C" int rsm_default_tree_root(void* /*user*/, int /*axis*/, uint32_t /*in
     *root_len = 32;
     return RSM_OK;
 }
+
+// ---- share inclusion proofs (include/rsmt2d_hip.h "share inclusion proofs") ----
+// Host restatements of the device node store + gather (kernels_proof.hip): the same
+// trees built level by level -- node (l, j) over leaves [j 2^l, min((j+1) 2^l, n)), an
+// unpaired last node carried up unchanged, which is the stack of perfect subtrees
+// above folded from the right -- keeping, at each level, the sibling of the node above
+// leaf `pos` where there is one.
+namespace {
+
+uint32_t proof_levels_of(uint32_t n) {  // ceil(log2 n)
+    uint32_t l = 0;
+    while ((1ull << l) < n) ++l;
+    return l;
+}
+
+// Walks the levels of a tree whose level-0 nodes are `lvl` (NB bytes each): `join`
+// hashes pair j of a level into `out` (false: tree error).  Fills the record; leaves
+// the root in lvl[0 .. NB).
+template <typename Join>
+bool prove_levels(std::vector<uint8_t>& lvl, uint32_t n, uint32_t NB, uint32_t pos, uint8_t* rec, Join&& join) {
+    const uint32_t L = proof_levels_of(n);
+    memset(rec, 0, 8 + (size_t)L * NB);
+    uint32_t n_nodes = 0, mask = 0, cnt = n;
+    std::vector<uint8_t> nxt;
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t j = pos >> l, sib = j ^ 1u;
+        if (sib < cnt) {
+            memcpy(rec + 8 + (size_t)n_nodes * NB, &lvl[(size_t)sib * NB], NB);
+            if (!(j & 1u)) mask |= 1u << n_nodes;  // the sibling is the right operand
+            ++n_nodes;
+        }
+        const uint32_t np = cnt / 2, up = (cnt + 1) / 2;
+        nxt.assign((size_t)up * NB, 0);
+        if (!join(lvl.data(), np, nxt.data())) return false;
+        if (cnt & 1u) memcpy(&nxt[(size_t)np * NB], &lvl[(size_t)(cnt - 1) * NB], NB);
+        lvl.swap(nxt);
+        cnt = up;
+    }
+    for (int b = 0; b < 4; ++b) {
+        rec[b] = (uint8_t)(n_nodes >> (8 * b));
+        rec[4 + b] = (uint8_t)(mask >> (8 * b));
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int rsm_default_tree_prove(const uint8_t* const* leaves, uint32_t n_leaves, uint32_t leaf_size, uint32_t pos,
+                                      uint8_t* record_out, uint8_t* root_out) {
+    if (!leaves || !record_out || n_leaves == 0 || pos >= n_leaves) return RSM_EINVAL;
+    for (uint32_t i = 0; i < n_leaves; ++i)
+        if (!leaves[i]) return RSM_ETREE;
+    std::vector<uint8_t> lvl((size_t)n_leaves * 32);
+    Digest dg[kHashBatch];
+    for (uint32_t i = 0; i < n_leaves; i += kHashBatch) {
+        const int c = (int)std::min<uint32_t>(kHashBatch, n_leaves - i);
+        hash_prefixed(0x00, leaves + i, c, leaf_size, dg);
+        for (int q = 0; q < c; ++q) memcpy(&lvl[(size_t)(i + q) * 32], dg[q].b, 32);
+    }
+    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) {
+        for (uint32_t j = 0; j < np; j += kHashBatch) {  // a pair is already the message body l || r
+            const int c = (int)std::min<uint32_t>(kHashBatch, np - j);
+            const uint8_t* m[kHashBatch];
+            for (int q = 0; q < c; ++q) m[q] = cur + (size_t)(j + q) * 64;
+            hash_prefixed(0x01, m, c, 64, dg);
+            for (int q = 0; q < c; ++q) memcpy(out + (size_t)(j + q) * 32, dg[q].b, 32);
+        }
+        return true;
+    };
+    prove_levels(lvl, n_leaves, 32, pos, record_out, join);
+    if (root_out) memcpy(root_out, lvl.data(), 32);
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_tree_prove(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves,
+                                  uint32_t n_leaves, uint32_t leaf_size, uint32_t pos, uint8_t* record_out,
+                                  uint8_t* root_out) {
+    if (!p || !leaves || !record_out || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
+        pos >= n_leaves)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    // erasuredNamespacedMerkleTree.Push, as rsm_nmt_tree_root
+    if (index + 1 > 2 * k || n_leaves > 2 * k) return RSM_ETREE;
+    if (leaf_size < nsz) return RSM_ETREE;
+    std::vector<uint8_t> parity(nsz, 0xFF);
+    const size_t ML = (size_t)nsz + leaf_size;
+    std::vector<uint8_t> msg((size_t)n_leaves * ML), lvl((size_t)n_leaves * NB);
+    const uint8_t* prev = nullptr;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (!leaves[i]) return RSM_ETREE;
+        const uint8_t* ns = (i < k && index < k) ? leaves[i] : parity.data();
+        if (prev && memcmp(ns, prev, nsz) < 0) return RSM_ETREE;
+        prev = ns;
+        memcpy(&msg[i * ML], ns, nsz);
+        memcpy(&msg[i * ML + nsz], leaves[i], leaf_size);
+        memcpy(&lvl[(size_t)i * NB], ns, nsz);
+        memcpy(&lvl[(size_t)i * NB + nsz], ns, nsz);
+    }
+    Digest dg[kHashBatch];
+    for (uint32_t i = 0; i < n_leaves; i += kHashBatch) {
+        const int c = (int)std::min<uint32_t>(kHashBatch, n_leaves - i);
+        const uint8_t* m[kHashBatch];
+        for (int q = 0; q < c; ++q) m[q] = &msg[(size_t)(i + q) * ML];
+        hash_prefixed(0x00, m, c, (uint32_t)ML, dg);
+        for (int q = 0; q < c; ++q) memcpy(&lvl[(size_t)(i + q) * NB + 2 * nsz], dg[q].b, 32);
+    }
+    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) {
+        for (uint32_t j = 0; j < np; j += kHashBatch) {
+            const int c = (int)std::min<uint32_t>(kHashBatch, np - j);
+            const uint8_t* m[kHashBatch];
+            for (int q = 0; q < c; ++q) {
+                const uint8_t* l = cur + (size_t)(2 * (j + q)) * NB;
+                if (!nmt_pair(l, l + NB, nsz, ig, out + (size_t)(j + q) * NB)) return false;
+                m[q] = l;
+            }
+            hash_prefixed(0x01, m, c, 2 * NB, dg);
+            for (int q = 0; q < c; ++q) memcpy(out + (size_t)(j + q) * NB + 2 * nsz, dg[q].b, 32);
+        }
+        return true;
+    };
+    if (!prove_levels(lvl, n_leaves, NB, pos, record_out, join)) return RSM_ETREE;
+    if (root_out) memcpy(root_out, lvl.data(), NB);
+    return RSM_OK;
+}

@@ -72,6 +72,14 @@ struct StreamScratch {
     DevBuf leaf;                  // DefaultTree leaf digests (device roots)
     DevBuf queue;                 // work-queue words of the single-launch extension
     HostBuf qerr;                 // its stuck-wait report (pinned, written by the device)
+    // rsm_proofs_dev: the caller's samples, staged (pinned) and on the device; samp_ev
+    // marks the last upload out of the staging buffer (waited for before it is reused)
+    HostBuf samp_host;
+    DevBuf samp_dev;
+    hipEvent_t samp_ev = nullptr;
+    ~StreamScratch() {
+        if (samp_ev) (void)hipEventDestroy(samp_ev);
+    }
 };
 
 // Buffers of the ExtendedDataSquare layer (Repair, device roots of an EDS):

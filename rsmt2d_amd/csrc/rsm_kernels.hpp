@@ -169,6 +169,56 @@ hipError_t launch_roots(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t s
 hipError_t launch_leaf_hashes(const uint8_t* d_cells, uint32_t cells, uint32_t S, uint32_t* d_leaf, hipStream_t st);
 hipError_t launch_tree_roots(const uint32_t* d_leaf, uint32_t W, uint32_t first, uint32_t count, uint8_t* d_roots,
                              hipStream_t st);
+// ---- share inclusion proofs (DESIGN.md §4 "Proofs") -----------------------------
+// The node store keeps every node of the 2W trees of `squares` squares, by levels: node
+// (l, j) of a tree covers leaves [j 2^l, min((j + 1) 2^l, W)); level l has
+// ceil(W / 2^l) nodes and an unpaired last node is carried up unchanged (a copy).
+// Words of the store:
+//   [squares][W * W][leaf_words]   level 0: the leaf records, one per cell (a cell's
+//                                  record serves its row tree and its column tree)
+//   [squares][2W][U][node_words]   levels 1 .. L of each tree (rows, then columns),
+//                                  level after level; U = proof_tree_nodes(W)
+// DefaultTree: leaf_words = node_words = 8 (the digest as big-endian words).  NMT:
+// leaf_words = 16 (namespace[8] | digest[8]), node_words = 24 (min[8] | max[8] | digest[8]).
+__host__ __device__ constexpr uint32_t proof_levels(uint32_t W) {  // ceil(log2 W)
+    uint32_t l = 0;
+    while ((1u << l) < W) ++l;
+    return l;
+}
+__host__ __device__ constexpr uint32_t proof_level_count(uint32_t W, uint32_t l) { return (W + (1u << l) - 1) >> l; }
+// index of node (l, 0) among a tree's nodes of levels 1 .. L (l >= 1)
+__host__ __device__ constexpr uint32_t proof_level_offset(uint32_t W, uint32_t l) {
+    uint32_t o = 0;
+    for (uint32_t i = 1; i < l; ++i) o += proof_level_count(W, i);
+    return o;
+}
+__host__ __device__ constexpr uint32_t proof_tree_nodes(uint32_t W) { return proof_level_offset(W, proof_levels(W) + 1); }
+constexpr uint32_t kProofShaWords = 8, kProofNmtLeafWords = 16, kProofNmtNodeWords = 24;
+__host__ __device__ constexpr uint64_t proof_store_words(uint32_t W, uint32_t squares, uint32_t leaf_words,
+                                                         uint32_t node_words) {
+    return (uint64_t)squares * ((uint64_t)W * W * leaf_words + (uint64_t)2 * W * proof_tree_nodes(W) * node_words);
+}
+// Node-store builds (kernels_sha.hip, kernels_nmt.hip): leaf records, then every tree
+// level written to the store as it is produced.  d_store 16-byte aligned; d_roots /
+// d_status nullable, laid out as launch_roots / launch_nmt_roots write them.
+uint32_t proof_trees_per_block(uint32_t W);  // trees a workgroup of either build takes (kernels_sha.hip)
+hipError_t launch_tree_nodes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t squares, uint32_t* d_store,
+                             uint8_t* d_roots, hipStream_t st);
+hipError_t launch_nmt_nodes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+                            uint32_t squares, uint32_t* d_store, uint8_t* d_roots, uint32_t* d_status, hipStream_t st);
+// A sample: leaf `pos` of row (axis 0) or column (axis 1) `index` of square `square`
+// (the C ABI's rsm_sample).
+struct ProofSample {
+    uint32_t square, axis, index, pos;
+};
+// Gather kernels (kernels_proof.hip).  ns = 0: DefaultTree store, else an NMT store
+// with ns-byte namespaces.  d_records: n records of 8 + L * node_len bytes.  d_shares
+// (16-byte aligned, like d_eds): n shares of S bytes.  Every sample must be in range:
+// the host validates them.
+hipError_t launch_proof_gather(const uint32_t* d_store, uint32_t W, uint32_t squares, uint32_t ns,
+                               const ProofSample* d_samples, uint32_t n, uint8_t* d_records, hipStream_t st);
+hipError_t launch_share_gather(const uint8_t* d_eds, uint32_t W, uint32_t S, const ProofSample* d_samples, uint32_t n,
+                               uint8_t* d_shares, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

@@ -1,0 +1,220 @@
+// rsm_proof.cpp -- share inclusion proofs: the C ABI over the node-store builds
+// (kernels_sha.hip, kernels_nmt.hip) and the gather kernels (kernels_proof.hip), and
+// rsm_eds_proofs of the ExtendedDataSquare object (device path with a cached node
+// store; host restatements of merkle.cpp otherwise).  Format: include/rsmt2d_hip.h.
+#include "eds_internal.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+using namespace rsm;
+
+static_assert(sizeof(rsm_sample) == sizeof(ProofSample) && sizeof(rsm_sample) == 16, "rsm_sample is the kernels' sample");
+
+namespace {
+
+hipStream_t pick(rsm_ctx* ctx, void* stream) { return stream ? static_cast<hipStream_t>(stream) : ctx->stream; }
+
+// The device tree of (width, nmt), or false beyond the root kernels' limits.
+bool proof_tree_for(uint32_t width, const rsm_nmt_params* nmt, DevTree* t) {
+    return device_tree_for(nmt ? rsm_nmt_tree_root : nullptr, const_cast<rsm_nmt_params*>(nmt), width, t);
+}
+
+uint64_t store_bytes(const DevTree& t, uint32_t W, uint32_t count) {
+    return 4 * (t.nmt ? proof_store_words(W, count, kProofNmtLeafWords, kProofNmtNodeWords)
+                      : proof_store_words(W, count, kProofShaWords, kProofShaWords));
+}
+
+// the first sample out of range, or n
+uint32_t first_bad_sample(const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (s[i].square >= count || s[i].axis > 1 || s[i].index >= width || s[i].pos >= width) return i;
+    return n;
+}
+
+int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
+    return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", who, i, s[i].square,
+                s[i].axis, s[i].index, s[i].pos);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t rsm_proof_nodes_bytes(uint32_t width, const rsm_nmt_params* nmt, uint32_t count) {
+    DevTree t;
+    if (!proof_tree_for(width, nmt, &t)) return 0;
+    if ((uint64_t)width * width * count >= (1ull << 32) || count > 65535) return 0;  // one launch
+    return store_bytes(t, width, count);
+}
+
+uint32_t rsm_proof_record_bytes(uint32_t width, const rsm_nmt_params* nmt) {
+    if (width == 0 || (nmt && nmt->namespace_size == 0)) return 0;
+    return 8 + proof_levels(width) * (nmt ? 2 * nmt->namespace_size + 32 : 32);
+}
+
+int rsm_proof_nodes_dev(rsm_ctx* ctx, const void* d_eds, uint32_t width, uint32_t share_size, uint32_t count,
+                        const rsm_nmt_params* nmt, void* d_nodes, void* d_roots, void* d_status, void* stream) {
+    if (!ctx || !d_eds || !d_nodes || width == 0) return fail(RSM_EINVAL, "rsm_proof_nodes_dev: bad arguments");
+    if ((reinterpret_cast<uintptr_t>(d_nodes) & 15u) || (reinterpret_cast<uintptr_t>(d_eds) & 15u))
+        return fail(RSM_EINVAL, "rsm_proof_nodes_dev: d_eds and d_nodes must be 16-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (share_size == 0) return fail(RSM_EINVAL, "rsm_proof_nodes_dev: empty shares");
+    DevTree t;
+    if (!proof_tree_for(width, nmt, &t) || (count && rsm_proof_nodes_bytes(width, nmt, count) == 0))
+        return fail(RSM_EUNSUPPORTED, "rsm_proof_nodes_dev: %u squares of width %u%s not supported", count, width,
+                    nmt ? " (NMT)" : "");
+    if (count == 0) return RSM_OK;
+    if (t.nmt && share_size < t.p.namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    hipError_t e;
+    if (t.nmt) {
+        e = launch_nmt_nodes(static_cast<const uint8_t*>(d_eds), width, share_size, t.p.namespace_size, t.p.square_size,
+                             t.p.ignore_max_namespace, count, static_cast<uint32_t*>(d_nodes),
+                             static_cast<uint8_t*>(d_roots), static_cast<uint32_t*>(d_status), st);
+    } else {
+        if (d_status && (e = hipMemsetAsync(d_status, 0, (size_t)count * 2 * width * 4, st)) != hipSuccess)
+            return hip_fail(e, "hipMemsetAsync (status)");
+        e = launch_tree_nodes(static_cast<const uint8_t*>(d_eds), width, share_size, count,
+                              static_cast<uint32_t*>(d_nodes), static_cast<uint8_t*>(d_roots), st);
+    }
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "node store kernel launch");
+}
+
+int rsm_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_t width, uint32_t share_size,
+                   uint32_t count, const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n, void* d_records,
+                   void* d_shares, void* stream) {
+    if (!ctx || !d_nodes || width == 0 || (n && (!samples || !d_records)))
+        return fail(RSM_EINVAL, "rsm_proofs_dev: bad arguments");
+    if (d_shares && !d_eds) return fail(RSM_EINVAL, "rsm_proofs_dev: d_shares needs d_eds");
+    if (d_shares && ((reinterpret_cast<uintptr_t>(d_shares) & 15u) || (reinterpret_cast<uintptr_t>(d_eds) & 15u)))
+        return fail(RSM_EINVAL, "rsm_proofs_dev: d_eds and d_shares must be 16-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    DevTree t;
+    if (!proof_tree_for(width, nmt, &t) || rsm_proof_nodes_bytes(width, nmt, count ? count : 1) == 0)
+        return fail(RSM_EUNSUPPORTED, "rsm_proofs_dev: %u squares of width %u%s not supported", count, width,
+                    nmt ? " (NMT)" : "");
+    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_dev: at most %u samples per call", 1u << 24);
+    const uint32_t bad = first_bad_sample(samples, n, count, width);
+    if (bad < n) return bad_sample("rsm_proofs_dev", samples, bad);
+    if (n == 0) return RSM_OK;
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    hipError_t e;
+    const size_t bytes = (size_t)n * sizeof(rsm_sample);
+    // the staging buffer is free once the previous call's upload has left it; the
+    // device copy is read by that call's kernels, ordered before this upload on `st`
+    if (ss.samp_ev && (e = hipEventSynchronize(ss.samp_ev)) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+    if (!ss.samp_ev && (e = hipEventCreateWithFlags(&ss.samp_ev, hipEventDisableTiming)) != hipSuccess) {
+        ss.samp_ev = nullptr;
+        return hip_fail(e, "hipEventCreate");
+    }
+    if (bytes > ss.samp_dev.cap) {
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+        if ((e = ss.samp_dev.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (samples)");
+    }
+    if ((e = ss.samp_host.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc (samples)");
+    memcpy(ss.samp_host.ptr, samples, bytes);
+    if ((e = hipMemcpyAsync(ss.samp_dev.ptr, ss.samp_host.ptr, bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return hip_fail(e, "H2D samples");
+    if ((e = hipEventRecord(ss.samp_ev, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    const auto* ds = static_cast<const ProofSample*>(ss.samp_dev.ptr);
+    if ((e = launch_proof_gather(static_cast<const uint32_t*>(d_nodes), width, count, t.nmt ? t.p.namespace_size : 0u,
+                                 ds, n, static_cast<uint8_t*>(d_records), st)) != hipSuccess)
+        return hip_fail(e, "proof gather kernel launch");
+    if (d_shares && (e = launch_share_gather(static_cast<const uint8_t*>(d_eds), width, share_size, ds, n,
+                                             static_cast<uint8_t*>(d_shares), st)) != hipSuccess)
+        return hip_fail(e, "share gather kernel launch");
+    return RSM_OK;
+}
+
+int rsm_eds_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
+                   uint8_t* records_out, uint8_t* shares_out) {
+    if (!e || (n && (!samples || !records_out))) return fail(RSM_EINVAL, "rsm_eds_proofs: bad arguments");
+    const rsm_nmt_params* nmt = nullptr;
+    if (tree_fn == rsm_nmt_tree_root && user) nmt = static_cast<const rsm_nmt_params*>(user);
+    else if (tree_fn != nullptr && tree_fn != rsm_default_tree_root)
+        return fail(RSM_EUNSUPPORTED, "rsm_eds_proofs: proofs are built for the DefaultTree and the NMT only");
+    const uint32_t W = e->width, S = e->S;
+    const uint32_t bad = first_bad_sample(samples, n, 1, W);
+    if (bad < n) return bad_sample("rsm_eds_proofs", samples, bad);
+    const uint32_t RB = rsm_proof_record_bytes(W, nmt);
+    if (n && RB == 0) return fail(RSM_EINVAL, "rsm_eds_proofs: namespace size 0");
+    auto cell_of = [&](const rsm_sample& s) { return e->cell(e->rr((int)s.axis, s.index, s.pos), e->cc((int)s.axis, s.index, s.pos)); };
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t p = 0; p < W; ++p)
+            if (!e->has(e->rr((int)samples[i].axis, samples[i].index, p), e->cc((int)samples[i].axis, samples[i].index, p)))
+                return fail(RSM_ETREE, "can not prove a share of incomplete %s %u", samples[i].axis == 0 ? "row" : "column",
+                            samples[i].index);
+    if (n == 0) return RSM_OK;
+    DevTree dt;
+    const bool complete = memchr(e->present.data(), 0, e->present.size()) == nullptr;
+    if (e->ctx && complete && proof_tree_for(W, nmt, &dt) && rsm_proof_nodes_bytes(W, nmt, 1) != 0 &&
+        (!dt.nmt || S >= dt.p.namespace_size)) {
+        rsm_ctx* ctx = e->ctx;
+        std::lock_guard<std::mutex> lk(ctx->eds_mu);
+        if (int rc = use_device(ctx)) return rc;
+        hipStream_t st = ctx->stream;
+        hipError_t r;
+        ProofStore& ps = e->proofs;
+        const bool same = ps.d_nodes && ps.ctx == ctx && ps.nmt == dt.nmt &&
+                          (!dt.nmt || memcmp(&ps.p, &dt.p, sizeof(dt.p)) == 0);
+        if (!same) {  // build the node store once; later calls only gather
+            ps.drop();
+            DevBuf& sq = ctx->eds.eds;
+            DevBuf& sb = ctx->eds.status;
+            if ((r = sq.ensure(e->data.size())) != hipSuccess || (r = sb.ensure((size_t)2 * W * 4)) != hipSuccess)
+                return hip_fail(r, "hipMalloc (proof square)");
+            if ((r = hipMalloc(&ps.d_nodes, store_bytes(dt, W, 1))) != hipSuccess) {
+                ps.d_nodes = nullptr;
+                return hip_fail(r, "hipMalloc (node store)");
+            }
+            ps.ctx = ctx;
+            ps.nmt = dt.nmt;
+            ps.p = dt.p;
+            ps.status.assign((size_t)2 * W, 0);
+            int rc = RSM_OK;
+            if ((r = hipMemcpyAsync(sq.ptr, e->data.data(), e->data.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
+                rc = hip_fail(r, "H2D square");
+            if (!rc) rc = rsm_proof_nodes_dev(ctx, sq.ptr, W, S, 1, nmt, ps.d_nodes, nullptr, sb.ptr, st);
+            if (!rc && (r = hipMemcpyAsync(ps.status.data(), sb.ptr, (size_t)2 * W * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+                rc = hip_fail(r, "D2H tree status");
+            if (!rc && (r = hipStreamSynchronize(st)) != hipSuccess) rc = hip_fail(r, "proof stream");
+            if (rc) {
+                ps.drop();
+                return rc;
+            }
+        }
+        for (uint32_t i = 0; i < n; ++i)
+            if (ps.status[(size_t)samples[i].axis * W + samples[i].index])
+                return fail(RSM_ETREE, "tree error proving a share of %s %u (namespace order)",
+                            samples[i].axis == 0 ? "row" : "column", samples[i].index);
+        DevBuf& rb = ctx->eds.scratch;
+        if ((r = rb.ensure((size_t)n * RB)) != hipSuccess) return hip_fail(r, "hipMalloc (proof records)");
+        if (int rc = rsm_proofs_dev(ctx, ps.d_nodes, nullptr, W, S, 1, nmt, samples, n, rb.ptr, nullptr, st)) return rc;
+        if ((r = hipMemcpyAsync(records_out, rb.ptr, (size_t)n * RB, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(r, "D2H proof records");
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(r, "proof stream");
+    } else {
+        std::vector<const uint8_t*> leaves(W);
+        for (uint32_t i = 0; i < n; ++i) {
+            const rsm_sample& s = samples[i];
+            for (uint32_t p = 0; p < W; ++p) leaves[p] = e->cell(e->rr((int)s.axis, s.index, p), e->cc((int)s.axis, s.index, p));
+            uint8_t* rec = records_out + (size_t)i * RB;
+            const int rc = nmt ? rsm_nmt_tree_prove(nmt, s.index, leaves.data(), W, S, s.pos, rec, nullptr)
+                               : rsm_default_tree_prove(leaves.data(), W, S, s.pos, rec, nullptr);
+            if (rc == RSM_ETREE)
+                return fail(RSM_ETREE, "tree error proving a share of %s %u", s.axis == 0 ? "row" : "column", s.index);
+            if (rc) return fail(rc, "rsm_eds_proofs: bad tree parameters");
+        }
+    }
+    if (shares_out)
+        for (uint32_t i = 0; i < n; ++i) memcpy(shares_out + (size_t)i * S, cell_of(samples[i]), S);
+    return RSM_OK;
+}
+
+}  // extern "C"

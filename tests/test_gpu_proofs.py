@@ -1,0 +1,270 @@
+"""GPU: share inclusion proofs from device-resident squares -- the node-store builds
+(kernels_sha.hip tree_nodes_kernel, kernels_nmt.hip nmt_nodes_kernel), the gather
+kernels (kernels_proof.hip) and the device path of rsm_eds_proofs.  Every record is
+byte-equal to the host restatement (merkle.cpp) and passes the independent verifier
+(tests/proof_verify.py) against oracle roots; d_roots / d_status equal what the root
+kernels write."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import rsmt2d_amd as R
+from oracle import crossword, nmt
+import proof_verify as V
+from conftest import const_share
+
+pytestmark = pytest.mark.gpu
+
+
+def all_samples(W, count=1):
+    return [(q, a, i, p) for q in range(count) for a in (0, 1) for i in range(W) for p in range(W)]
+
+
+def picked_samples(W, seed, count=1, n=256):
+    """The four corners, both sides of the k boundary on both axes, n seeded samples."""
+    k = W // 2
+    s = {(0, a, i, p) for a in (0, 1) for i in (0, W - 1) for p in (0, W - 1)}
+    s |= {(0, a, i, p) for a in (0, 1) for i in (k - 1, k) for p in (k - 1, k)}
+    rng = np.random.default_rng(seed)
+    s |= {(int(rng.integers(count)), int(rng.integers(2)), int(rng.integers(W)), int(rng.integers(W))) for _ in range(n)}
+    return sorted(s)
+
+
+class Dev:
+    """One node-store build + one gather over a [count][W][W][S] batch."""
+
+    def __init__(self, lib, batch, p, samples, with_roots=True):
+        self.count, self.W, _, self.S = batch.shape
+        W, S, count, n = self.W, self.S, self.count, len(samples)
+        ctx = R.device_context(0)
+        pp = ctypes.byref(p) if p is not None else None
+        self.nl = 32 if p is None else 2 * p.namespace_size + 32
+        self.rb = int(lib.rsm_proof_record_bytes(W, pp))
+        assert self.rb == V.record_bytes(W, self.nl)
+        nbytes = int(lib.rsm_proof_nodes_bytes(W, pp, count))
+        assert nbytes > 0
+        bufs = [R.DeviceBuffer(batch.nbytes), R.DeviceBuffer(nbytes), R.DeviceBuffer(count * 2 * W * self.nl),
+                R.DeviceBuffer(count * 2 * W * 4), R.DeviceBuffer(n * self.rb), R.DeviceBuffer(n * S),
+                R.DeviceBuffer(count * 2 * W * self.nl), R.DeviceBuffer(count * 2 * W * 4)]
+        d, nodes, roots, status, recs, shs, roots2, status2 = bufs
+        try:
+            d.upload(batch.reshape(-1))
+            status.upload(np.full(count * 2 * W, 0xFFFFFFFF, np.uint32).view(np.uint8))
+            arr = (R.Sample * n)(*[R.Sample(*s) for s in samples])
+            R._check(lib.rsm_proof_nodes_dev(ctx, d.ptr, W, S, count, pp, nodes.ptr, roots.ptr if with_roots else None,
+                                             status.ptr if with_roots else None, None))
+            R._check(lib.rsm_proofs_dev(ctx, nodes.ptr, d.ptr, W, S, count, pp, arr, n, recs.ptr, shs.ptr, None))
+            del arr  # copied before the call returned
+            if p is None:
+                R._check(lib.rsm_roots_squares_dev(ctx, d.ptr, W, S, count, roots2.ptr, None))
+            else:
+                R._check(lib.rsm_nmt_roots_squares_dev(ctx, d.ptr, W, S, count, pp, roots2.ptr, status2.ptr, None))
+            R._check(lib.rsm_sync(ctx))
+            self.records = recs.download().tobytes()
+            self.shares = shs.download().tobytes()
+            self.roots, self.roots_ref = roots.download().tobytes(), roots2.download().tobytes()
+            self.status = status.download().view(np.uint32).copy()
+            self.status_ref = status2.download().view(np.uint32).copy() if p is not None else np.zeros_like(self.status)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def record(self, i):
+        return self.records[i * self.rb:(i + 1) * self.rb]
+
+    def share(self, i):
+        return self.shares[i * self.S:(i + 1) * self.S]
+
+
+def host_record(lib, p, leaves, index, pos):
+    keep, ptrs, _ = R._bufs(leaves)
+    nl = 32 if p is None else 2 * p.namespace_size + 32
+    rec = ctypes.create_string_buffer(V.record_bytes(len(leaves), nl))
+    if p is None:
+        rc = lib.rsm_default_tree_prove(ptrs, len(leaves), len(leaves[0]), pos, rec, None)
+    else:
+        rc = lib.rsm_nmt_tree_prove(ctypes.byref(p), index, ptrs, len(leaves), len(leaves[0]), pos, rec, None)
+    assert rc == 0
+    return rec.raw
+
+
+def check_samples(lib, dev, batch, p, samples, skip_trees=()):
+    """Records byte-equal to the host restatement and verified against the oracle root
+    of their tree; gathered shares equal to the cells."""
+    W = dev.W
+    vec, want = {}, {}
+    for i, (q, a, idx, pos) in enumerate(samples):
+        cell = batch[q, idx, pos] if a == 0 else batch[q, pos, idx]
+        assert dev.share(i) == cell.tobytes(), (q, a, idx, pos)
+        if (q, a, idx) in skip_trees:
+            continue
+        key = (q, a, idx)
+        if key not in vec:
+            vec[key] = V.vector(batch[q], a, idx)
+            want[key] = (crossword.merkle_root(vec[key]) if p is None else
+                         nmt.erasured_root(vec[key], idx, p.square_size, p.namespace_size))
+        rec = dev.record(i)
+        assert rec == host_record(lib, p, vec[key], idx, pos), (q, a, idx, pos)
+        nodes, mask = V.parse_record(rec, dev.nl)
+        assert len(nodes) == V.level_count(W, pos)
+        if p is None:
+            assert V.verify_default(want[key], [vec[key][pos]] + nodes, pos, W), (q, a, idx, pos)
+        else:
+            assert V.verify_nmt(want[key], vec[key][pos], nodes, mask, pos, idx, p.square_size, p.namespace_size)
+
+
+@pytest.mark.parametrize("W,S", [(2, 64), (4, 64), (6, 64), (10, 128), (14, 64), (24, 64), (70, 64), (128, 64),
+                                 (200, 576), (256, 512)])
+def test_default_tree_proofs_dev(lib, W, S):
+    batch = V.rand_square(W, S, 10 * W + S)[None]
+    samples = all_samples(W) if W <= 24 else picked_samples(W, W)
+    dev = Dev(lib, batch, None, samples)
+    assert dev.roots == dev.roots_ref  # byte-equal to rsm_roots_dev
+    assert not dev.status.any()
+    check_samples(lib, dev, batch, None, samples)
+
+
+@pytest.mark.parametrize("k,ns,S", [(1, 29, 64), (3, 8, 128), (5, 29, 64), (12, 29, 64), (16, 1, 64), (35, 29, 64),
+                                    (64, 32, 512), (128, 29, 512)])
+def test_nmt_proofs_dev(lib, k, ns, S):
+    W = 2 * k
+    batch = V.sorted_q0_square(k, S, ns, 100 * k + ns)[None]
+    p = R.NmtParams(ns, 1, k)
+    samples = all_samples(W) if W <= 24 else picked_samples(W, W + ns)
+    dev = Dev(lib, batch, p, samples)
+    assert dev.roots == dev.roots_ref  # byte-equal to rsm_nmt_roots_dev
+    assert not dev.status.any() and not dev.status_ref.any()
+    check_samples(lib, dev, batch, p, samples)
+
+
+@pytest.mark.parametrize("W", [24, 128])
+@pytest.mark.parametrize("tree", ["default", "nmt"])
+def test_batches(lib, W, tree):
+    k, S, ns, count = W // 2, 64, 29, 3
+    batch = np.stack([V.sorted_q0_square(k, S, ns, 7000 + W + q) for q in range(count)])
+    p = R.NmtParams(ns, 1, k) if tree == "nmt" else None
+    samples = picked_samples(W, 5 * W, count=count, n=192)
+    samples += [(q, a, i, p_) for (_, a, i, p_) in samples[:16] for q in (1, 2)]  # every square has samples
+    dev = Dev(lib, batch, p, samples)
+    assert dev.roots == dev.roots_ref and (dev.status == dev.status_ref).all() and not dev.status.any()
+    check_samples(lib, dev, batch, p, samples)
+
+
+@pytest.mark.parametrize("W", [24, 128])
+def test_nmt_batch_with_unordered_row(lib, W):
+    """Square 1 has row 0 out of namespace order: its status equals the root kernel's,
+    every other tree's proofs are unaffected."""
+    k, S, ns, count = W // 2, 64, 29, 3
+    batch = np.stack([V.sorted_q0_square(k, S, ns, 9000 + W + q) for q in range(count)])
+    batch[1, 0, 0, :ns] = 0xEE
+    batch[1, 0, 1, :ns] = 0x01
+    p = R.NmtParams(ns, 1, k)
+    samples = picked_samples(W, 3 * W, count=count, n=192) + [(1, 0, 0, 5), (1, 0, 1, 0), (1, 1, 2, 0), (1, 1, 3, 1)]
+    dev = Dev(lib, batch, p, samples)
+    st = dev.status.reshape(count, 2 * W)
+    assert (dev.status == dev.status_ref).all() and dev.roots == dev.roots_ref
+    assert st[1, 0] != 0 and not st[0].any() and not st[2].any()
+    failing = {(1, t // W, t % W) for t in np.nonzero(st[1])[0]}
+    assert (1, 0, 1) not in failing and (1, 1, 2) not in failing
+    check_samples(lib, dev, batch, p, samples, skip_trees=failing)
+
+
+def test_width_limit_and_unsupported(lib):
+    W, S = 1024, 64
+    samples = [(0, 0, 0, 0), (0, 0, W - 1, W - 1), (0, 1, 0, W - 1), (0, 1, W - 1, 0), (0, 0, 511, 512), (0, 1, 512, 511),
+               (0, 0, 300, 777), (0, 1, 901, 2)]
+    batch = V.sorted_q0_square(W // 2, S, 29, 4242)[None]
+    for p in (None, R.NmtParams(29, 1, W // 2)):
+        dev = Dev(lib, batch, p, samples)
+        assert dev.roots == dev.roots_ref and not dev.status.any()
+        check_samples(lib, dev, batch, p, samples)
+    ctx = R.device_context(0)
+    small = R.DeviceBuffer(4096)
+    smp = (R.Sample * 1)(R.Sample(0, 0, 0, 0))
+    for width, p in [(4096, None), (2048, R.NmtParams(29, 1, 1024)), (1024, R.NmtParams(32, 1, 512)), (1, None),
+                     (8, R.NmtParams(29, 1, 2))]:
+        pp = ctypes.byref(p) if p is not None else None
+        assert lib.rsm_proof_nodes_bytes(width, pp, 1) == 0
+        assert lib.rsm_proof_nodes_dev(ctx, small.ptr, width, 64, 1, pp, small.ptr, None, None, None) == R.RSM_EUNSUPPORTED
+        assert lib.rsm_proofs_dev(ctx, small.ptr, None, width, 64, 1, pp, smp, 1, small.ptr, None, None) == R.RSM_EUNSUPPORTED
+    # bad samples are refused before anything is enqueued
+    for s in [(1, 0, 0, 0), (0, 2, 0, 0), (0, 0, 8, 0), (0, 0, 0, 8)]:
+        two = (R.Sample * 2)(R.Sample(0, 0, 0, 0), R.Sample(*s))
+        assert lib.rsm_proofs_dev(ctx, small.ptr, None, 8, 64, 1, None, two, 2, small.ptr, None, None) == R.RSM_EINVAL
+        assert b"sample 1" in lib.rsm_last_error()
+    small.free()
+
+
+def _verify(pr, root, tree, k, ns):
+    if tree == "default":
+        return V.verify_default(root, pr.proofSet(), pr.index, pr.numLeaves)
+    return V.verify_nmt(root, pr.share, pr.nodes, pr.right_mask, pr.index, pr.tree_index, k, ns)
+
+
+@pytest.mark.parametrize("tree", ["default", "nmt"])
+def test_eds_proofs_device_path(lib, tree):
+    k, S, ns = 16, 64, 29
+    W = 2 * k
+    ods = V.sorted_q0_square(k, S, ns, 77)[:k, :k]
+    ctor = R.NewDefaultTree if tree == "default" else R.newErasuredNamespacedMerkleTreeConstructor(k, ns)
+    eds = R.ComputeExtendedDataSquare([ods[r, c].tobytes() for r in range(k) for c in range(k)], R.NewLeoRSCodec(), ctor)
+    rr, cr = eds.RowRoots(), eds.ColRoots()
+    flat = eds.Flattened()
+    samples = [(a, i, p) for a in (0, 1) for i in range(W) for p in range(W)]
+    proofs = eds.Proofs(samples)
+    for (a, i, p), pr in zip(samples, proofs):
+        r, c = (i, p) if a == 0 else (p, i)
+        assert pr.share == flat[r * W + c]
+        assert _verify(pr, (rr if a == 0 else cr)[i], tree, k, ns), (a, i, p)
+        assert pr.root == (rr if a == 0 else cr)[i]
+    rp, cp = eds.RowProof(3, 20), eds.ColProof(3, 20)
+    assert rp.share == cp.share == flat[3 * W + 20] and (rp.index, cp.index) == (20, 3)
+    assert _verify(rp, rr[3], tree, k, ns) and _verify(cp, cr[20], tree, k, ns)
+    # the same bytes again, from the cached store
+    again = eds.Proofs(samples)
+    assert all(x.nodes == y.nodes and x.right_mask == y.right_mask and x.share == y.share for x, y in zip(proofs, again))
+    # the host path (no context) gives the same records
+    host = R.ImportExtendedDataSquare(flat, R.NewLeoRSCodec(), ctor)
+    some = samples[::37]
+    assert [(x.nodes, x.right_mask) for x in host.Proofs(some)] == [(x.nodes, x.right_mask) for x in proofs[::37]]
+    # setCell drops the store: the proof follows the new root
+    old = eds.RowProof(5, 9)
+    share = bytearray(flat[5 * W + 9])
+    share[-1] ^= 0x5A
+    eds.setCell(5, 9, bytes(share))
+    rr2, cr2 = eds.RowRoots(), eds.ColRoots()
+    new_r, new_c = eds.RowProof(5, 9), eds.ColProof(5, 9)
+    assert rr2[5] != rr[5] and new_r.share == bytes(share)
+    assert _verify(new_r, rr2[5], tree, k, ns) and _verify(new_c, cr2[9], tree, k, ns)
+    assert not _verify(new_r, rr[5], tree, k, ns)
+    assert new_r.nodes == old.nodes  # the siblings of the changed leaf did not change ...
+    nb = eds.RowProof(5, 8)          # ... its neighbour's proof did
+    assert nb.nodes[0] != proofs[samples.index((0, 5, 8))].nodes[0] and _verify(nb, rr2[5], tree, k, ns)
+
+
+def test_fraud_proof_with_share_proofs(lib):
+    """The set-up of test_valid_fraud_proof (extendeddatacrossword_test.go:116-163): the
+    byzantine vector's present shares, each with a proof in its orthogonal tree against
+    the committed roots -- the "Merkle proof for each share" of the reference's TODO."""
+    S = 512
+    codec = R.NewLeoRSCodec()
+    original = R.ComputeExtendedDataSquare([const_share(v, S) for v in (1, 2, 3, 4)], codec, R.NewDefaultTree)
+    corrupted = original.deepCopy(codec)
+    corrupted.setCell(0, 0, bytes([66]) * S)
+    rr, cr = corrupted.RowRoots(), corrupted.ColRoots()
+    with pytest.raises(R.ErrByzantineData) as ei:
+        corrupted.Repair(rr, cr)
+    byz = ei.value
+    checked = 0
+    for j, share in enumerate(byz.Shares):
+        if share is None:
+            continue
+        if byz.Axis == R.Row:
+            pr, root = corrupted.ColProof(byz.Index, j), cr[j]
+        else:
+            pr, root = corrupted.RowProof(j, byz.Index), rr[j]
+        assert pr.share == share and pr.index == byz.Index
+        assert V.verify_default(root, pr.proofSet(), pr.index, pr.numLeaves)
+        checked += 1
+    assert checked == len(byz.Shares) == 4
