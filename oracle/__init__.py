@@ -6,9 +6,14 @@ leg may import this package.  The product (``rsmt2d_amd``) never does.
 * ``libleopard_oracle.so`` (built from ``leopard_oracle.c`` by ``make``) is a scalar C
   restatement of klauspost/reedsolomon v1.14.1's Leopard codec as configured by
   rsmt2d's ``LeoRSCodec`` (``leopard.go:28-72``).  That Go module is absent from
-  ``/root/reference`` and no Go toolchain exists here, so parity is pinned only by
-  the reference's own known-answer grids (``extendeddatasquare_test.go:39-59``);
-  every larger size is "parity unpinned vs LeoRSCodec" (DESIGN.md).
+  ``/root/reference`` and no Go toolchain exists here.  The restatement is pinned at
+  every size class to the algebraic definition of the code
+  (``tests/test_definition_cpu.py`` over ``tests/rs_definition.py``: encode,
+  extend_square and decode of consistent input), and the definition's constants and
+  point order are pinned to the reference by its own known-answer grids
+  (``extendeddatasquare_test.go:39-59``, the 2x2 one).  klauspost itself is still
+  absent, and decode of INCONSISTENT input (the byzantine formula) is still
+  restatement-only (DESIGN.md).
 * ``crossword.py`` restates ``extendeddatacrossword.go`` (Repair) in Python over this
   codec, for small squares.
 """

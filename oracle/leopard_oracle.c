@@ -9,9 +9,11 @@
  *   - GF(2^16) ("leopard.go")   when 2k > 256     (codecs.go:6-10)
  * That module is NOT present in /root/reference and there is no Go toolchain
  * here, so this is a restatement of its published algorithm (SURVEY.md
- * Appendix A).  Parity is pinned only by the reference's own known-answer
- * tests (extendeddatasquare_test.go:39-59, the 1x1 and 2x2 grids); every other
- * size is "parity unpinned vs LeoRSCodec" (see DESIGN.md / tests/golden).
+ * Appendix A).  It is pinned at every size class to the algebraic definition of
+ * the code (tests/test_definition_cpu.py), whose constants and point order the
+ * reference's own known-answer tests pin (extendeddatasquare_test.go:39-59, the
+ * 1x1 and 2x2 grids); decode of inconsistent input is restatement-only (see
+ * DESIGN.md / tests/golden).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
  * load this library.  It is deliberately simple scalar C (one 256-entry

@@ -441,8 +441,8 @@ int extend_squares_queue(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, u
 int extend_squares_split(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count, hipStream_t st) {
     const uint32_t M = ceil_pow2(k);
     if (field_bits(k) != 8 || count == 0) return RSM_EUNSUPPORTED;
-    // M = 32 / 64 (round 6): the split form too (encode_gf8_splitm_kernel) for up to
-    // split_max squares; larger batches take the byte-table passes
+    // 9 <= k <= 64 (M = 16, 32, 64; round 6): the split form too (encode_gf8_splitm_kernel)
+    // for up to split_max squares; larger batches take the byte-table passes
     if (M != 128 && M != 16 && M != 32 && M != 64) return RSM_EUNSUPPORTED;
     const CodewordSet rows = rows_set(d_eds, k, S, count);
     CodewordSet c0 = cols_set(d_eds, k, S, count);  // columns 0 .. k-1 (Q0 -> Q2)

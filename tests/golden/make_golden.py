@@ -3,12 +3,17 @@
 Sources:
 * kat_grids.json -- copied DATA (expected grids) from the reference's own known-answer
   test, extendeddatasquare_test.go:39-59 (TestComputeExtendedDataSquare "1x1" and "2x2";
-  each share is S copies of the listed byte).  These are the only reference-pinned values.
+  each share is S copies of the listed byte).  These are the only values copied from
+  the reference.
 * restatement.json -- SHA-256 digests / spot values produced by the CPU oracle
   (oracle/leopard_oracle.c) on the SURVEY.md Appendix B affine input.  They agree with
-  the independent survey-time restatement's published digests, but are
-  "parity unpinned vs LeoRSCodec" (klauspost/reedsolomon v1.14.1 is absent here).
-* eds_k{3,4,8}_s64.npy -- full EDS bytes of the oracle on the affine input (unpinned).
+  the independent survey-time restatement's published digests.  The oracle that made
+  them is pinned at every size class to the algebraic definition of the code
+  (tests/test_definition_cpu.py), whose constants and point order the 2x2 grid above
+  pins to the reference; klauspost/reedsolomon v1.14.1 itself is still absent here, and
+  decode of inconsistent input is still restatement-only.
+* eds_k{3,4,8}_s64.npy -- full EDS bytes of the oracle on the affine input (the same
+  standing).
 
 Run:  python tests/golden/make_golden.py
 """
@@ -29,6 +34,11 @@ KAT = {
     "2x2": {"ods": [[1, 2], [3, 4]],
             "eds": [[1, 2, 0, 3], [3, 4, 8, 15], [2, 11, 13, 4], [0, 13, 5, 8]]},
 }
+
+RESTATEMENT_NOTE = ("oracle restatement values; the restatement is pinned at every size class to the algebraic "
+                    "definition of the code (tests/test_definition_cpu.py), whose constants and point order the "
+                    "reference's 2x2 grid pins; klauspost itself is absent, and decode of inconsistent input is "
+                    "restatement-only")
 
 SURVEY_DIGESTS = [  # SURVEY.md Appendix B (survey-time restatement)
     (2, 64, 8, "c181edd583289d2ee360159a5a05a9cde90f345e777c0233156b1bb5fe29a9f4"),
@@ -67,7 +77,7 @@ def main():
             data.append(bytes(b))
         p = oracle.encode(data)[0]
         spot.append({"k": k, "parity0": [p[j] if k <= 128 else p[j] | (p[32 + j] << 8) for j in range(4)]})
-    json.dump({"note": "oracle restatement values; parity unpinned vs LeoRSCodec beyond k=2",
+    json.dump({"note": RESTATEMENT_NOTE,
                "affine_digests_survey": rows, "affine_digests_more": extra, "spot_parity0": spot},
               open(os.path.join(HERE, "restatement.json"), "w"), indent=1)
     for k in (3, 4, 8):

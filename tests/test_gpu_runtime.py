@@ -412,7 +412,7 @@ def test_multi_gpu_inplace_pinned_world1(lib, multi, sched):
                                        (64, 512, 12), (64, 128, 13), (24, 1024, 5), (32, 128, 64), (64, 64, 65),
                                        (9, 64, 1), (16, 512, 1), (13, 192, 7), (16, 64, 70)])
 def test_small_square_latency_form(lib, k, S, count):
-    """17 <= k <= 64: up to 64 squares per call take the split latency form
+    """9 <= k <= 64 (M = 16, 32, 64): up to 64 squares per call take the split latency form
     (encode_gf8_splitm_kernel), larger batches the byte-table passes; both == oracle."""
     W = 2 * k
     n = W * W * S * count
