@@ -205,8 +205,6 @@ DIAG_SIGNATURES = {
     "rsm_diag_set_dec_trace": (_I32, [_VP]),
     "rsm_diag_set_split_waves": (_I32, [ctypes.c_int, ctypes.c_int]),
     "rsm_diag_set_split_fused": (_I32, [ctypes.c_int]),
-    "rsm_diag_set_enc16_e64": (_I32, [ctypes.c_int]),
-    "rsm_diag_set_dec16_five_pass": (_I32, [ctypes.c_int]),
     "rsm_diag_set_dec_delay": (_I32, [ctypes.c_uint32]),
     "rsm_diag_set_dec8_mode": (_I32, [ctypes.c_uint32]),
     "rsm_diag_set_codec_spin": (_I32, [ctypes.c_uint32]),

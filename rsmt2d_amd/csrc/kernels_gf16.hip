@@ -6,23 +6,20 @@
 // bytes, 4 hi bytes), so a wavefront spans 8 blocks = 512 bytes of share width
 // and every multiply-by-constant is 12 v_perm_b32 lookups (PermTab16).
 //
-// Encode (m = ceilPow2(k) in {256, 512}) is ONE pass per codeword: a workgroup owns a
-// (codeword, chunk) and keeps its m-point IFFT + FFT on chip (m = 256: 256-byte chunks,
-// one element per lane-half, enc16h_kernel; m = 512 as follows) -- a workgroup of
-// m/32 waves, each holding E = 32 elements of a 512-byte chunk in registers; one LDS exchange
-// buffer ([element][lane] dwords, one plane at a time) switches between
-//   group layout   (wave w: elements 32 w .. 32 w + 31):  layers d < 32
-//   residue layout (wave w: residues r = (32/R) w + s, elements r + 32 j, j < R =
-//                   m/32):                                 layers d = 32 .. m/2
-// so the data shares are read once and the parity shares written once.
-// The decoder's n = 2m transforms still run as radix-16 passes through a global
-// work array ([codeword][element][S]):
-//   decode (n = 2m): 1 group: scale by the error locator + IFFT low
-//                    2 residue: IFFT high; also H(in) = high-bit half of the formal derivative
-//                    3 group: out = in + L(in) + H(in)  (the derivative's closed form)
-//                    4 residue: FFT high          5 group: FFT low + reveal
-// Every wave works on one (codeword, 512-byte chunk, group|residue) task, so all
-// lanes share each twiddle (wave-uniform SGPR table loads).
+// m = ceilPow2(k) in {256, 512}: encode and decode are ONE pass per codeword.  A
+// workgroup owns a (codeword, chunk) task and keeps the whole m-point IFFT + FFT
+// (encode: enc16h_kernel, enc16h512_kernel) or n = 2m-point IFFT + formal derivative
+// + FFT (decode: dec16f_kernel, dec16h_kernel, behind errloc16_kernel) on chip: the
+// elements sit in registers, the twiddle tables in LDS, and an LDS exchange buffer
+// (one plane at a time) switches between
+//   group layout   (consecutive elements per wave or lane-half):  the low layers
+//   residue layout (elements a fixed stride apart):               the high layers
+// so the shares are read once and the parity / rebuilt shares written once.
+// m >= 1024 (and the wide forms): radix-16 passes through a global work array
+// (g16_pass_kernel and friends, below), every wave on one (codeword, 512-byte chunk,
+// group) task, so all lanes share each twiddle (wave-uniform SGPR table loads).
+// The forms these replaced, and what each lost by, are recorded in DESIGN.md and
+// profiles/.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
@@ -84,7 +81,7 @@ struct Sel16 {
     uint32_t a, b, c, d, e, f;
 };
 __device__ __forceinline__ Sel16 sel16(uint32_t yl, uint32_t yh) {
-#ifdef RSM_SEL32  // (diagnostic A/B builds only: the round-5 selectors, four 32-bit shifts)
+#ifdef RSM_SEL32  // (diagnostic A/B builds only: the selectors as four 32-bit shifts)
     return Sel16{yl & 0x07070707u, (yl >> 3) & 0x07070707u, (yl >> 6) & 0x03030303u,
                  yh & 0x07070707u, (yh >> 3) & 0x07070707u, (yh >> 6) & 0x03030303u};
 #endif
@@ -133,85 +130,6 @@ __device__ __forceinline__ void fft2(uint32_t& xl, uint32_t& xh, uint32_t& yl, u
     yh ^= xh;
 }
 
-// Group layout: 16 consecutive elements 16g..16g+15.  IFFT layers d = 1..8, block b
-// uses SKEW[OFF + b + d]; FFT layers d = 8..1 use SKEW[OFF2 + b + d].
-__device__ __forceinline__ void group_ifft(uint32_t (&l)[16], uint32_t (&h)[16], uint32_t g, int off, const Res& r) {
-    sfor<4>([&](auto LG) {
-        constexpr int d = 1 << decltype(LG)::value;
-        sfor<8>([&](auto Q) {
-            constexpr int q = decltype(Q)::value;
-            constexpr int bl = (q / d) * 2 * d;
-            constexpr int i = bl + (q % d);
-            const uint32_t L = skew_at(r, off + (int)(16 * g) + bl + d);
-            ifft2(l[i], h[i], l[i + d], h[i + d], L, r);
-        });
-    });
-}
-__device__ __forceinline__ void group_fft(uint32_t (&l)[16], uint32_t (&h)[16], uint32_t g, const Res& r) {
-    sfor<4>([&](auto LG) {
-        constexpr int d = 8 >> decltype(LG)::value;
-        sfor<8>([&](auto Q) {
-            constexpr int q = decltype(Q)::value;
-            constexpr int bl = (q / d) * 2 * d;
-            constexpr int i = bl + (q % d);
-            const uint32_t L = skew_at(r, (int)(16 * g) + bl + d - 1);
-            fft2(l[i], h[i], l[i + d], h[i + d], L, r);
-        });
-    });
-}
-// Residue layout: R elements rho + 16 j.  Element distance D = 16 d', block
-// b = 16 * (j-block start).
-template <int R>
-__device__ __forceinline__ void residue_ifft(uint32_t (&l)[R], uint32_t (&h)[R], int off, const Res& r) {
-    sfor<12>([&](auto LG) {
-        constexpr int d = 1 << decltype(LG)::value;
-        if constexpr (d < R) {
-            sfor<R / 2>([&](auto Q) {
-                constexpr int q = decltype(Q)::value;
-                constexpr int bl = (q / d) * 2 * d;
-                constexpr int i = bl + (q % d);
-                const uint32_t L = skew_at(r, off + 16 * bl + 16 * d);
-                ifft2(l[i], h[i], l[i + d], h[i + d], L, r);
-            });
-        }
-    });
-}
-template <int R>
-__device__ __forceinline__ void residue_fft(uint32_t (&l)[R], uint32_t (&h)[R], const Res& r) {
-    sfor<12>([&](auto LG) {
-        constexpr int d = 2048 >> decltype(LG)::value;
-        if constexpr (d < R) {
-            sfor<R / 2>([&](auto Q) {
-                constexpr int q = decltype(Q)::value;
-                constexpr int bl = (q / d) * 2 * d;
-                constexpr int i = bl + (q % d);
-                const uint32_t L = skew_at(r, 16 * bl + 16 * d - 1);
-                fft2(l[i], h[i], l[i + d], h[i + d], L, r);
-            });
-        }
-    });
-}
-
-// closed-form formal derivative restricted to one coordinate:
-//   D'(x)[j] = XOR_{t: bit t of j == 0, j + 2^t < N} x[j + 2^t]   (without the x[j] term)
-template <int N>
-__device__ __forceinline__ void deriv_terms(const uint32_t (&xl)[N], const uint32_t (&xh)[N], uint32_t (&ol)[N],
-                                            uint32_t (&oh)[N]) {
-    sfor<N>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        uint32_t al = 0, ah = 0;
-        sfor<12>([&](auto T) {
-            constexpr int t = decltype(T)::value;
-            if constexpr ((1 << t) < N && ((j >> t) & 1) == 0 && j + (1 << t) < N) {
-                al ^= xl[j + (1 << t)];
-                ah ^= xh[j + (1 << t)];
-            }
-        });
-        ol[j] = al;
-        oh[j] = ah;
-    });
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
     const uint64_t a = reinterpret_cast<uint64_t>(p);
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
@@ -242,22 +160,6 @@ __device__ __forceinline__ uint64_t cw_rel(const CodewordSet& cs, uint32_t q) {
     const uint32_t sq = q / cs.per_square;
     const uint32_t t = q - sq * cs.per_square;
     return (uint64_t)sq * cs.square_stride + (uint64_t)t * cs.cw_stride;
-}
-
-struct TaskIdx {
-    uint32_t q, chunk, g;
-    bool valid;
-};
-__device__ __forceinline__ TaskIdx task_of(uint32_t count, uint32_t chunks, uint32_t groups) {
-    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    TaskIdx t{};
-    t.valid = w < count * chunks * groups;
-    if (!t.valid) return t;
-    t.g = w % groups;
-    const uint32_t r = w / groups;
-    t.chunk = r % chunks;
-    t.q = r / chunks;
-    return t;
 }
 
 // ---------------------------------------------------------------------------
@@ -293,16 +195,10 @@ __device__ __forceinline__ void muladd16v(uint32_t& xl, uint32_t& xh, uint32_t y
             x3(pm(c[9], c[9], sc), pm(c[13], c[12], sd), pm(c[17], c[16], se)), pm(c[19], c[19], sf));
 }
 typedef uint32_t v4u16 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void tab_load(const uint32_t* lds, uint32_t (&c)[kTabW]) {
-    sfor<kTabW / 4>([&](auto Q) {
-        constexpr int q = decltype(Q)::value;
-        const v4u16 v = *reinterpret_cast<const v4u16*>(lds + 4 * q);
-        c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
-    });
-}
-// The same as ONE asm statement that waits for its own reads: the compiler can
-// neither hoist a later block's table above the butterflies nor keep several tables
-// live (the 128-register 16-wave kernels spilled ~700 dwords with tab_load).
+// Read a compact table from LDS just in time: ONE asm statement that waits for its own
+// reads, so the compiler can neither hoist a later block's table above the butterflies
+// nor keep several tables live (with compiler-scheduled reads the 128-register 16-wave
+// kernels spilled ~700 dwords).
 __device__ __forceinline__ void tab_load_jit(const uint32_t* lds, uint32_t (&c)[kTabW]) {
     v4u16 a, b, e, f, g;
     const uint32_t base = (uint32_t)(uintptr_t)lds;
@@ -346,17 +242,7 @@ __device__ __forceinline__ void tab_load_jit_at(const uint32_t* lds, uint32_t (&
     c[12] = f.x; c[13] = f.y; c[14] = f.z; c[15] = f.w;
     c[16] = g.x; c[17] = g.y; c[18] = g.z; c[19] = g.w;
 }
-// Butterflies with the twiddle table given directly (zero table = no multiply).
-__device__ __forceinline__ void ifft2t(uint32_t& xl, uint32_t& xh, uint32_t& yl, uint32_t& yh, const PermTab16& t) {
-    yl ^= xl;
-    yh ^= xh;
-    muladd16(xl, xh, yl, yh, t);
-}
-__device__ __forceinline__ void fft2t(uint32_t& xl, uint32_t& xh, uint32_t& yl, uint32_t& yh, const PermTab16& t) {
-    muladd16(xl, xh, yl, yh, t);
-    yl ^= xl;
-    yh ^= xh;
-}
+// Butterflies with the twiddle's compact table in VGPRs (zero table = no multiply).
 __device__ __forceinline__ void ifft2v(uint32_t& xl, uint32_t& xh, uint32_t& yl, uint32_t& yh, const uint32_t (&c)[kTabW]) {
     yl ^= xl;
     yh ^= xh;
@@ -441,8 +327,9 @@ __device__ __forceinline__ void stage_res(uint32_t* tab, const PermTab16* tw, in
 }
 
 // Group layout (E elements per wave): IFFT layers d = 1..E/2 ascending / FFT
-// d = E/2..1 descending; the table of (layer, block) from this wave's E-1 slots.
-template <int E, bool FFT, bool JIT = false>
+// d = E/2..1 descending; the table of (layer, block) from this wave's E-1 slots,
+// read just in time (the decoders; the encoders read one block ahead, grp_xform_pipe).
+template <int E, bool FFT>
 __device__ __forceinline__ void grp_xform(uint32_t (&l)[E], uint32_t (&h)[E], const uint32_t* wtab) {
     constexpr int LN = ilog2c(E);
     sfor<LN>([&](auto LGi) {
@@ -451,39 +338,18 @@ __device__ __forceinline__ void grp_xform(uint32_t (&l)[E], uint32_t (&h)[E], co
         sfor<E / 2 / d>([&](auto Bk) {
             constexpr int block = decltype(Bk)::value;
             uint32_t c[kTabW];
-            if constexpr (JIT) tab_load_jit_at<(E - (E >> L) + block) * kTabW * 4>(wtab, c);
-            else tab_load(wtab + (E - (E >> L) + block) * kTabW, c);
+            tab_load_jit_at<(E - (E >> L) + block) * kTabW * 4>(wtab, c);
             sfor<d>([&](auto Q) {
                 constexpr int i = block * 2 * d + decltype(Q)::value;
                 if constexpr (FFT) fft2v(l[i], h[i], l[i + d], h[i + d], c);
                 else ifft2v(l[i], h[i], l[i + d], h[i + d], c);
-                // JIT: pin the block's butterflies before the next block's table read
-                if constexpr (JIT) asm volatile("" : "+v"(l[i]), "+v"(h[i]), "+v"(l[i + d]), "+v"(h[i + d]));
+                // pin the block's butterflies before the next block's table read
+                asm volatile("" : "+v"(l[i]), "+v"(h[i]), "+v"(l[i + d]), "+v"(h[i + d]));
             });
         });
     });
 }
-// The same with each table read straight from global memory (wave-uniform:
-// scalar loads), for the 16-wave m = 512 form whose registers leave no room for
-// LDS-staged tables: IFFT SKEW[off + base + b + d], FFT SKEW[base + b + d - 1].
-template <int E, bool FFT>
-__device__ __forceinline__ void grp_xform_g(uint32_t (&l)[E], uint32_t (&h)[E], const PermTab16* tw, int base, int off) {
-    constexpr int LN = ilog2c(E);
-    sfor<LN>([&](auto LGi) {
-        constexpr int L = FFT ? LN - 1 - decltype(LGi)::value : decltype(LGi)::value;
-        constexpr int d = 1 << L;
-        sfor<E / 2 / d>([&](auto Bk) {
-            constexpr int bl = decltype(Bk)::value * 2 * d;
-            const PermTab16& t = tw[FFT ? base + bl + d - 1 : off + base + bl + d];
-            sfor<d>([&](auto Q) {
-                constexpr int i = bl + decltype(Q)::value;
-                if constexpr (FFT) fft2t(l[i], h[i], l[i + d], h[i + d], t);
-                else ifft2t(l[i], h[i], l[i + d], h[i + d], t);
-            });
-        });
-    });
-}
-// Software-pipelined table reads (round 6): the NEXT block's table is read while this
+// Software-pipelined table reads: the NEXT block's table is read while this
 // block's butterflies run, the wait sits after them.  tab_issue_at puts the five
 // ds_read_b128 in flight without a wait; tab_wait waits for them and, through its "+v"
 // operands, is the point from which the compiler may read them.  The caller pins each
@@ -574,8 +440,9 @@ constexpr int res_pipe_slot(int n) {
     const int L = pipe_layer<R, NL, FFT>(n), b = pipe_block<R, NL, FFT>(n);
     return (FFT ? R - 1 : 0) + (R - (R >> L)) + b;
 }
-// res_xform (one residue per lane group, E == R, MERGED: the top layer is res_mid) with
-// pipelined table reads: IFFT slots 0..R-2, FFT slots R-1..2R-3 of rtab
+// The encoders' residue layers below the top one (which is res_mid), one residue of R
+// elements per lane-half, with pipelined table reads: IFFT slots 0..R-2, FFT slots
+// R-1..2R-3 of rtab
 template <int R, bool FFT>
 __device__ __forceinline__ void res_xform_pipe(uint32_t (&l)[R], uint32_t (&h)[R], const uint32_t* rtab) {
     constexpr int NL = ilog2c(R) - 1, NB = R - 2;  // layers dj = 1 .. R/4 (the merged top excluded)
@@ -601,115 +468,53 @@ __device__ __forceinline__ void res_xform_pipe(uint32_t (&l)[R], uint32_t (&h)[R
     });
 }
 
-// Residue-layout register of (residue s of the wave, j): s R + j (the full-buffer
-// exchange), or -- IL, the half-buffer exchange -- (E / R) j + s, so that the
-// registers a wave sends in one pass of xch_plane_half are exactly the ones it
-// receives into (element bit 0 = s picks the pass in both layouts).
+// Residue-layout register of (residue s of the wave, j): s R + j, or -- IL, the
+// half-buffer exchange of dec16f_kernel -- (E / R) j + s, so that the registers a
+// wave sends in one pass of xch_plane_half are exactly the ones it receives into
+// (element bit 0 = s picks the pass in both layouts).
 template <int E, int R, bool IL>
 constexpr int ridx(int s, int j) { return IL ? (E / R) * j + s : s * R + j; }
 
-template <int E, int R, bool FFT, bool MERGED = false, bool IL = false>
-__device__ __forceinline__ void res_xform_g(uint32_t (&l)[E], uint32_t (&h)[E], const PermTab16* tw, int off) {
-    constexpr int LN = ilog2c(R), NL = MERGED ? LN - 1 : LN;  // MERGED: the top layer is res_mid
-    sfor<NL>([&](auto LGi) {
-        constexpr int L = FFT ? NL - 1 - decltype(LGi)::value : decltype(LGi)::value;
-        constexpr int dj = 1 << L;
-        sfor<R / 2 / dj>([&](auto Bk) {
-            constexpr int bl = decltype(Bk)::value * 2 * dj;
-            const PermTab16& t = tw[FFT ? E * bl + E * dj - 1 : off + E * bl + E * dj];
-            sfor<dj>([&](auto Q) {
-                constexpr int j = bl + decltype(Q)::value;
-                sfor<E / R>([&](auto Sx) {
-                    constexpr int i = ridx<E, R, IL>(decltype(Sx)::value, j), i2 = ridx<E, R, IL>(decltype(Sx)::value, j + dj);
-                    if constexpr (FFT) fft2t(l[i], h[i], l[i2], h[i2], t);
-                    else ifft2t(l[i], h[i], l[i2], h[i2], t);
-                });
-            });
-        });
-    });
-}
-// The merged top pair of the residue layers (elements E R / 2 = m / 2 apart), see Enc16::mid.
-template <int E, int R, bool IL = false>
-__device__ __forceinline__ void res_mid(uint32_t (&l)[E], uint32_t (&h)[E], const PermTab16* mid) {
+// The merged top pair of the encoders' residue layers (one residue of R elements per
+// lane-half, register j; the pair's elements are m / 2 apart), see Enc16::mid.
+template <int R>
+__device__ __forceinline__ void res_mid(uint32_t (&l)[R], uint32_t (&h)[R], const PermTab16* mid) {
     constexpr int dj = R / 2;
     if (!mid) return;  // y ^= x twice: the identity
     const PermTab16& t = *mid;
-    sfor<E / R>([&](auto Sx) {
-        sfor<dj>([&](auto Q) {
-            constexpr int i = ridx<E, R, IL>(decltype(Sx)::value, decltype(Q)::value);
-            constexpr int i2 = ridx<E, R, IL>(decltype(Sx)::value, decltype(Q)::value + dj);
-            l[i2] ^= l[i];
-            h[i2] ^= h[i];
-            muladd16(l[i], h[i], l[i2], h[i2], t);
-            l[i2] ^= l[i];
-            h[i2] ^= h[i];
-        });
+    sfor<dj>([&](auto Q) {
+        constexpr int i = decltype(Q)::value, i2 = i + dj;
+        l[i2] ^= l[i];
+        h[i2] ^= h[i];
+        muladd16(l[i], h[i], l[i2], h[i2], t);
+        l[i2] ^= l[i];
+        h[i2] ^= h[i];
     });
 }
-// The same with the table read from LDS (mtab: kTabW words, staged from Enc16::mid).
-template <int E, int R, bool IL, bool JIT>
-__device__ __forceinline__ void res_mid_v(uint32_t (&l)[E], uint32_t (&h)[E], const uint32_t* mtab) {
-    constexpr int dj = R / 2;
-    uint32_t c[kTabW];
-    if constexpr (JIT) tab_load_jit(mtab, c);
-    else tab_load(mtab, c);
-    sfor<E / R>([&](auto Sx) {
-        sfor<dj>([&](auto Q) {
-            constexpr int i = ridx<E, R, IL>(decltype(Sx)::value, decltype(Q)::value);
-            constexpr int i2 = ridx<E, R, IL>(decltype(Sx)::value, decltype(Q)::value + dj);
-            l[i2] ^= l[i];
-            h[i2] ^= h[i];
-            muladd16v(l[i], h[i], l[i2], h[i2], c);
-            l[i2] ^= l[i];
-            h[i2] ^= h[i];
-            if constexpr (JIT) asm volatile("" : "+v"(l[i]), "+v"(h[i]), "+v"(l[i2]), "+v"(h[i2]));
-        });
-    });
-}
-// Residue layout: register s*R + j holds element r_s + E j; a layer over j at
-// distance dj joins elements E dj apart (block start E bl): one table per
-// (layer, block) for every residue of every wave.
-template <int E, int R, bool FFT, bool MERGED = true, bool JIT = false, bool IL = false>
+// Residue layout of the decoders: register ridx(s, j) holds element r_s + E j; a layer
+// over j at distance dj joins elements E dj apart (block start E bl): one table per
+// (layer, block) for every residue of every wave, read just in time.
+template <int E, int R, bool FFT, bool IL>
 __device__ __forceinline__ void res_xform(uint32_t (&l)[E], uint32_t (&h)[E], const uint32_t* rtab) {
-    constexpr int LN = ilog2c(R), NL = MERGED ? LN - 1 : LN;
-    sfor<NL>([&](auto LGi) {  // MERGED: the top layer (dj = R/2) is res_mid
-        constexpr int L = FFT ? NL - 1 - decltype(LGi)::value : decltype(LGi)::value;
+    constexpr int LN = ilog2c(R);
+    sfor<LN>([&](auto LGi) {
+        constexpr int L = FFT ? LN - 1 - decltype(LGi)::value : decltype(LGi)::value;
         constexpr int dj = 1 << L;
         sfor<R / 2 / dj>([&](auto Bk) {
             constexpr int block = decltype(Bk)::value;
             uint32_t c[kTabW];
-            if constexpr (JIT) tab_load_jit(rtab + ((FFT ? R - 1 : 0) + (R - (R >> L)) + block) * kTabW, c);
-            else tab_load(rtab + ((FFT ? R - 1 : 0) + (R - (R >> L)) + block) * kTabW, c);
+            tab_load_jit(rtab + ((FFT ? R - 1 : 0) + (R - (R >> L)) + block) * kTabW, c);
             sfor<dj>([&](auto Q) {
                 constexpr int j = block * 2 * dj + decltype(Q)::value;
                 sfor<E / R>([&](auto Sx) {
                     constexpr int i = ridx<E, R, IL>(decltype(Sx)::value, j), i2 = ridx<E, R, IL>(decltype(Sx)::value, j + dj);
                     if constexpr (FFT) fft2v(l[i], h[i], l[i2], h[i2], c);
                     else ifft2v(l[i], h[i], l[i2], h[i2], c);
-                    if constexpr (JIT) asm volatile("" : "+v"(l[i]), "+v"(h[i]), "+v"(l[i2]), "+v"(h[i2]));
+                    asm volatile("" : "+v"(l[i]), "+v"(h[i]), "+v"(l[i2]), "+v"(h[i2]));
                 });
             });
         });
     });
-}
-
-// One plane of the layout switch through LDS xch[element][lane].  Residue
-// register s*R + j holds element (E/R) w + s + E j.
-template <int E, int R, bool TO_RESIDUE>
-__device__ __forceinline__ void xch_plane(uint32_t (&v)[E], uint32_t (*xch)[64], uint32_t w, uint32_t lane) {
-    constexpr int RPW = E / R;  // residues per wave
-    sfor<E>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        const uint32_t e = TO_RESIDUE ? E * w + i : (RPW * w + i / R) + E * (i % R);
-        xch[e][lane] = v[i];
-    });
-    __syncthreads();
-    sfor<E>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        const uint32_t e = TO_RESIDUE ? (RPW * w + i / R) + E * (i % R) : E * w + i;
-        v[i] = xch[e][lane];
-    });
-    __syncthreads();
 }
 
 // One plane of the layout switch through HALF an element-indexed buffer xch[N/2][64]
@@ -748,141 +553,23 @@ __device__ __forceinline__ void xch_plane_half(uint32_t (&v)[E], uint32_t (*xch)
     });
 }
 
-// Encoder: parity of codeword q, chunk c (512 bytes) = FFT(IFFT(data)).  The
-// encoder's IFFT uses SKEW[m - 1 + b + d] (data occupy the upper half of the
-// 2m-point domain), its FFT SKEW[b + d - 1]; every index is < 2m <= kSkewPermN.
-// Twiddle tables: staged in LDS per workgroup (the group stages' 31 per wave in
-// the exchange buffer, which is idle then; the residue stages' in rtab), read by
-// uniform ds_read_b128 -- a table load from L2 per butterfly would leave the waves
-// waiting on scalar loads (the tables of one transform exceed the scalar cache).
-// m/32 waves of E = 32 elements; residues of R = m/32 elements.
-//   m = 256: 8 waves (2 per SIMD, up to 256 registers), persistent (one workgroup
-//            per CU), twiddle tables staged once into LDS and read by uniform
-//            ds_read_b128 -- one scalar table load from L2 per butterfly left the
-//            waves waiting (the tables of a transform exceed the scalar cache);
-//   m = 512: 16 waves (128 registers each, no room for LDS-read tables), one
-//            workgroup per task, tables by scalar loads (A/B: faster here).
-// E = 64 (m = 512 only, round 3q): 8 waves of 64 elements, 256 registers each (the
-// 16-wave form is held to 128 registers and spills 44 dwords per lane); the merged
-// middle pair is affordable there.
-// HX (m = 512, 16 waves; production HX = 3 since round 4): persistent, the twiddle
-// tables staged in LDS beside HALF an exchange buffer (two passes per plane,
-// xch_plane_half, the IL residue register order); the top residue layer pair is not
-// merged (128 registers).  1.5-2.5 % faster than the round-3 form with scalar-loaded
-// tables (HX = 0, one workgroup per task) -- the tables were not what held it at ~5.8
-// cycles per VALU instruction.
-// HX bits: 1 half exchange buffer (persistent), 2 LDS tables, 4 just-in-time table reads,
-// 8 the merged middle residue pair (res_mid)
-template <int M, int E = 32, int HX = 0>
-__global__ __launch_bounds__(M * 64 / E, HX ? 4 : ((M == 256 && E == 32) ? 2 : (E <= 32 ? 4 : 1))) void enc16_kernel(Enc16 p) {
-    constexpr int WAVES = M / E, R = M / E;
-    constexpr bool LDS_TAB = M == 256 || (HX & 2);
-    constexpr bool JIT = (HX & 4) != 0;
-    constexpr bool MID = (HX & 8) != 0;  // the merged middle pair (res_mid)
-    static_assert(!HX || E == 32, "HX: waves of 32 elements");
-    constexpr int GT = WAVES * (E - 1) * kTabW;
-    __shared__ uint32_t xch[HX ? M / 2 : M][64];
-    __shared__ uint32_t tabs[LDS_TAB ? 2 * GT + (2 * (R - 1) + (MID ? 1 : 0)) * kTabW : 1];
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    uint32_t* gI = tabs;
-    uint32_t* gF = tabs + GT;
-    uint32_t* rtab = tabs + 2 * GT;
-    if constexpr (LDS_TAB) {
-        stage_grp<WAVES, E, false>(gI, p.tw, M - 1);
-        stage_grp<WAVES, E, true>(gF, p.tw, 0);
-        stage_res<R, E, WAVES * 64>(rtab, p.tw, M - 1);
-        if constexpr (MID)
-            if (p.mid && threadIdx.x < (uint32_t)kTabW) rtab[2 * (R - 1) * kTabW + threadIdx.x] = p.mid->w[tab_word((int)threadIdx.x)];
-    }
-    const uint32_t es = (uint32_t)p.cs.elem_stride, k = p.cs.k;
-    const uint32_t oo = (uint32_t)p.cs.out_offset;
-    const uint32_t tasks = p.cs.count * p.chunks;
-    auto run = [&](uint32_t task) {
-        const uint32_t q = task / p.chunks, chunk = task - q * p.chunks;
-        const Lane ln = lane_of(chunk, p.cs.S);
-        const uint64_t rel = cw_rel(p.cs, q);
-        const auto in = rsrc(p.cs.base + rel);
-        uint32_t l[E], h[E];
-        sfor<E>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            const uint32_t e = E * w + i;
-            const uint32_t so = e < k ? e * es : kOob16;
-            l[i] = ld(in, ln.lo, so);
-            h[i] = ld(in, ln.lo + 32, so);
-        });
-        if constexpr (HX != 0) {
-            __syncthreads();  // tables staged (first task)
-            if constexpr (LDS_TAB) grp_xform<E, false, JIT>(l, h, gI + w * (E - 1) * kTabW);
-            else grp_xform_g<E, false>(l, h, p.tw, (int)(E * w), M - 1);
-            xch_plane_half<E, R, true>(l, xch, w, lane);
-            xch_plane_half<E, R, true>(h, xch, w, lane);
-            if constexpr (LDS_TAB) {
-                res_xform<E, R, false, MID, JIT, true>(l, h, rtab);
-                if constexpr (MID)
-                    if (p.mid) res_mid_v<E, R, true, JIT>(l, h, rtab + 2 * (R - 1) * kTabW);
-                res_xform<E, R, true, MID, JIT, true>(l, h, rtab);
-            } else {
-                res_xform_g<E, R, false, false, true>(l, h, p.tw, M - 1);
-                res_xform_g<E, R, true, false, true>(l, h, p.tw, 0);
-            }
-            xch_plane_half<E, R, false>(l, xch, w, lane);
-            xch_plane_half<E, R, false>(h, xch, w, lane);
-            if constexpr (LDS_TAB) grp_xform<E, true, JIT>(l, h, gF + w * (E - 1) * kTabW);
-            else grp_xform_g<E, true>(l, h, p.tw, (int)(E * w), 0);
-        } else {
-        if constexpr (LDS_TAB) {
-            __syncthreads();  // tables staged (first task)
-            grp_xform<E, false>(l, h, gI + w * (E - 1) * kTabW);
-        } else {
-            grp_xform_g<E, false>(l, h, p.tw, (int)(E * w), M - 1);
-        }
-        xch_plane<E, R, true>(l, xch, w, lane);
-        xch_plane<E, R, true>(h, xch, w, lane);
-        if constexpr (LDS_TAB) {
-            res_xform<E, R, false>(l, h, rtab);
-            res_mid<E, R>(l, h, p.mid);
-            res_xform<E, R, true>(l, h, rtab);
-        } else if constexpr (E == 64) {  // m = 512, 256 registers: the merged middle pair
-            res_xform_g<E, R, false, true>(l, h, p.tw, M - 1);
-            res_mid<E, R>(l, h, p.mid);
-            res_xform_g<E, R, true, true>(l, h, p.tw, 0);
-        } else {  // m = 512, 16 waves: not merged (its 128-register form spills more with it: c5 0.58 -> 0.70 ms)
-            res_xform_g<E, R, false>(l, h, p.tw, M - 1);
-            res_xform_g<E, R, true>(l, h, p.tw, 0);
-        }
-        xch_plane<E, R, false>(l, xch, w, lane);
-        xch_plane<E, R, false>(h, xch, w, lane);
-        if constexpr (LDS_TAB) grp_xform<E, true>(l, h, gF + w * (E - 1) * kTabW);
-        else grp_xform_g<E, true>(l, h, p.tw, (int)(E * w), 0);
-        }
-        const auto out = rsrc(p.cs.out_base + rel);
-        sfor<E>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            const uint32_t e = E * w + i;
-            const uint32_t so = e < k ? oo + e * es : kOob16;
-            st(out, l[i], ln.lo, so);
-            st(out, h[i], ln.lo + 32, so);
-        });
-    };
-    if constexpr (LDS_TAB) {
-        for (uint32_t task = blockIdx.x; task < tasks; task += gridDim.x) run(task);
-    } else {
-        run(blockIdx.x);  // grid = tasks
-    }
-}
-
-// Half-wave form of the m = 256 encoder (round 4): one task per (codeword, 256-byte
-// chunk), so each lane-half (32 lanes x 4 symbols = 256 bytes) holds ONE element's
-// chunk and every register two elements: half g = 2 w + (lane >> 5) of wave w.
-//   group layout   (half g: elements 16 g .. 16 g + 15):  layers d = 1..8, each half
-//                  reading its own twiddle tables (per-lane LDS address: one address
-//                  per 16-lane LDS group, a broadcast)
-//   residue layout (half g: elements g + 16 j, j < 16):  layers d = 16..128, tables
-//                  shared by all lanes
-// State is 32 registers per lane and the LDS 73 KiB (one plane of a [256][32]
-// exchange buffer + the tables), so TWO 8-wave workgroups share a CU: one's loads and
-// stores overlap the other's butterflies (the 512-byte-chunk forms hold 128 KiB of
-// state per task and run one workgroup per CU, their memory phases exposed).
+// ---------------------------------------------------------------------------
+// Encoders: parity of codeword q, 256-byte chunk c = FFT(IFFT(data)).  The encoder's
+// IFFT uses SKEW[m - 1 + b + d] (data occupy the upper half of the 2m-point domain),
+// its FFT SKEW[b + d - 1]; every index is < 2m <= kSkewPermN.  Persistent workgroups
+// stage every twiddle table in LDS once (a table load from L2 per butterfly block
+// leaves the waves waiting on scalar loads: the tables of one transform exceed the
+// scalar cache) and read them one block ahead of the butterflies (grp_xform_pipe,
+// res_xform_pipe).  The 512-byte-chunk forms with 32 or 64 elements per wave, scalar-
+// loaded or just-in-time tables, a prefetch of the next task's points and a three-
+// workgroup m = 256 form all measured slower: DESIGN.md, "GF(2^16) kernels", and
+// profiles/r04k_gf16_enc_ab.jsonl, r04q_gf16_enc_ab.jsonl, r04aa_gf16_enc_ab.jsonl,
+// r06i_gf16_pipe_ab.jsonl.
+// SH: 0 plain, 1 / 2 the multi-GPU all-to-all's row pass with side output / column
+// pass with blocked inputs (CodewordSet::side / blk).
+// ---------------------------------------------------------------------------
+// The group <-> residue exchange of one plane through xch[M][32]: a lane-half moves
+// its E registers in one pass.
 template <int E>
 __device__ __forceinline__ void xch_halfwave(uint32_t (&v)[E], uint32_t (*xch)[32], uint32_t g, uint32_t l32, bool to_res) {
     sfor<E>([&](auto I) {
@@ -897,41 +584,22 @@ __device__ __forceinline__ void xch_halfwave(uint32_t (&v)[E], uint32_t (*xch)[3
     __syncthreads();
 }
 
-// The group <-> residue exchange of enc16h_body through an [M][XL] buffer: XL = 32 moves
-// a whole half per pass (xch_halfwave), XL = 8 a quarter of its lanes per pass (four
-// passes, a quarter of the LDS).
-template <int E, int XL>
-__device__ __forceinline__ void xch_part(uint32_t (&v)[E], uint32_t (*xch)[XL], uint32_t g, uint32_t l32, bool to_res) {
-    const uint32_t ls = l32 % XL, sub = l32 / XL;
-    sfor<32 / XL>([&](auto Pc) {
-        constexpr uint32_t pp = decltype(Pc)::value;
-        if (sub == pp)
-            sfor<E>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                xch[to_res ? E * g + i : g + E * i][ls] = v[i];
-            });
-        __syncthreads();
-        if (sub == pp)
-            sfor<E>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                v[i] = xch[to_res ? g + E * i : E * g + i][ls];
-            });
-        __syncthreads();
-    });
-}
-
-// PF: the next task's points are loaded while the current one transforms
-// XL: lanes per exchange pass (32: production, two workgroups per CU; 8: the 49 KiB form,
-// enc16h3_kernel, three workgroups per CU at 80 registers)
-// PIPE (production since round 6; PIPE = false is diagnostic form 22): twiddle tables read
-// one block ahead (grp_xform_pipe / res_xform_pipe) instead of just in time
-// SH (round 6): 0 plain, 1 / 2 the multi-GPU all-to-all's row pass with side output /
-// column pass with blocked inputs (CodewordSet::side / blk)
-template <bool JIT, bool PF, int XL, bool PIPE = false, int SH = 0>
+// Half-wave form of the m = 256 encoder: one task per (codeword, 256-byte chunk), so
+// each lane-half (32 lanes x 4 symbols = 256 bytes) holds ONE element's chunk and
+// every register two elements: half g = 2 w + (lane >> 5) of wave w.
+//   group layout   (half g: elements 16 g .. 16 g + 15):  layers d = 1..8, each half
+//                  reading its own twiddle tables (per-lane LDS address: one address
+//                  per 16-lane LDS group, a broadcast)
+//   residue layout (half g: elements g + 16 j, j < 16):  layers d = 16..128, tables
+//                  shared by all lanes
+// State is 32 registers per lane and the LDS 73 KiB (one plane of a [256][32]
+// exchange buffer + the tables), so TWO 8-wave workgroups share a CU: one's loads and
+// stores overlap the other's butterflies.
+template <int SH>
 __device__ __forceinline__ void enc16h_body(const Enc16& p) {
     constexpr int M = 256, E = 16, G = 16, R = 16, THREADS = 512;
     constexpr int GT = G * (E - 1) * kTabW;
-    __shared__ uint32_t xch[M][XL];
+    __shared__ uint32_t xch[M][32];
     __shared__ uint32_t tabs[2 * GT + 2 * (R - 1) * kTabW];
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const uint32_t hh = lane >> 5, l32 = lane & 31u, g = 2u * w + hh;
@@ -997,41 +665,26 @@ __device__ __forceinline__ void enc16h_body(const Enc16& p) {
         });
         if constexpr (SH == 1) side_store(qq, lo, lim, l, h, 0u);
     };
-    uint32_t nl[E], nh[E];
-    if constexpr (PF)
-        if (blockIdx.x < tasks) load_task(blockIdx.x, nl, nh);
     for (uint32_t task = blockIdx.x; task < tasks; task += gridDim.x) {
         const uint32_t q = task / p.chunks;
         const uint32_t lo = lane_off(task);
         const uint64_t rel = cw_rel(p.cs, q);
         uint32_t l[E], h[E];
-        if constexpr (PF) {
-            sfor<E>([&](auto I) {
-                l[decltype(I)::value] = nl[decltype(I)::value];
-                h[decltype(I)::value] = nh[decltype(I)::value];
-            });
-            if (task + gridDim.x < tasks) load_task(task + gridDim.x, nl, nh);
-        } else {
-            load_task(task, l, h);
-        }
-        if constexpr (PIPE) grp_xform_pipe<E, false>(l, h, tI);
-        else grp_xform<E, false, JIT>(l, h, tI);
-        xch_part<E, XL>(l, xch, g, l32, true);
-        xch_part<E, XL>(h, xch, g, l32, true);
-        if constexpr (PIPE) res_xform_pipe<R, false>(l, h, rtab);
-        else res_xform<E, R, false, true, JIT>(l, h, rtab);
-        res_mid<E, R>(l, h, p.mid);
-        if constexpr (PIPE) res_xform_pipe<R, true>(l, h, rtab);
-        else res_xform<E, R, true, true, JIT>(l, h, rtab);
-        xch_part<E, XL>(l, xch, g, l32, false);
-        xch_part<E, XL>(h, xch, g, l32, false);
-        if constexpr (PIPE) grp_xform_pipe<E, true>(l, h, tF);
-        else grp_xform<E, true, JIT>(l, h, tF);
+        load_task(task, l, h);
+        grp_xform_pipe<E, false>(l, h, tI);
+        xch_halfwave<E>(l, xch, g, l32, true);
+        xch_halfwave<E>(h, xch, g, l32, true);
+        res_xform_pipe<R, false>(l, h, rtab);
+        res_mid<R>(l, h, p.mid);
+        res_xform_pipe<R, true>(l, h, rtab);
+        xch_halfwave<E>(l, xch, g, l32, false);
+        xch_halfwave<E>(h, xch, g, l32, false);
+        grp_xform_pipe<E, true>(l, h, tF);
         const auto out = rsrc(p.cs.out_base + rel);
         // the store offsets are recomputed here from opaque copies (the compiler would
         // otherwise keep the load phase's 16 per-lane offsets alive across the transform)
         uint32_t slo = lo, slim = lim;
-#ifndef RSM_ENC16_HOISTED_OFFSETS  // (diagnostic A/B builds: the round-5 hoisted offsets)
+#ifndef RSM_ENC16_HOISTED_OFFSETS  // (diagnostic A/B builds: the hoisted offsets)
         asm volatile("" : "+v"(slo), "+v"(slim));
 #endif
         sfor<E>([&](auto I) {
@@ -1045,18 +698,15 @@ __device__ __forceinline__ void enc16h_body(const Enc16& p) {
     }
 }
 
-template <bool JIT, bool PF = false, bool PIPE = false, int SH = 0>
+// (the body stays a function of its own: written straight into the kernel it compiles
+// to different code)
+template <int SH>
 __global__ __launch_bounds__(512, 4) void enc16h_kernel(Enc16 p) {
-    enc16h_body<JIT, PF, 32, PIPE, SH>(p);
+    enc16h_body<SH>(p);
 }
-// three workgroups per CU: 6 waves per SIMD (80 registers), 49 KiB of LDS each
-__global__ __launch_bounds__(512, 6) void enc16h3_kernel(Enc16 p) {
-    enc16h_body<true, false, 8>(p);
-}
-
-// Half-wave form of the m = 512 encoder (round 4): one task per (codeword, 256-byte
-// chunk), 16 waves, half g = 2 w + (lane >> 5) holding elements 16 g .. 16 g + 15 in
-// its registers (32 state registers, against 64 for 512-byte chunks):
+// Half-wave form of the m = 512 encoder: one task per (codeword, 256-byte chunk), 16
+// waves, half g = 2 w + (lane >> 5) holding elements 16 g .. 16 g + 15 in its
+// registers (32 state registers):
 //   layers d = 1..8   in registers, per-half tables (as enc16h_kernel);
 //   layer  d = 16     joins the two halves of a wave: v_permlane32_swap of the register
 //                     pairs (i, i + 1) puts elements 32 w + i + hh and 32 w + 16 + i + hh
@@ -1073,10 +723,7 @@ __device__ __forceinline__ uint32_t swapped_elem(uint32_t w, int r, uint32_t hh)
     return 32u * w + ((r & 1) ? 16u : 0u) + (uint32_t)(r & ~1) + hh;
 }
 
-// PF: the next task's points are loaded while the current one transforms (32 more registers)
-// PIPE (production since round 6; PIPE = false is diagnostic form 22): twiddle tables
-// read one block ahead
-template <bool JIT, bool PF = false, bool PIPE = false, int SH = 0>
+template <int SH>
 __global__ __launch_bounds__(1024, 4) void enc16h512_kernel(Enc16 p) {
     constexpr int M = 512, E = 16, G = 32, R = 16, THREADS = 1024;
     constexpr int GT = G * (E - 1) * kTabW, WT = 16 * kTabW, RT = 2 * (R - 1) * kTabW;
@@ -1158,25 +805,13 @@ __global__ __launch_bounds__(1024, 4) void enc16h512_kernel(Enc16 p) {
         });
         if constexpr (SH == 1) side_store(qq, lo, lim, l, h, 0u);
     };
-    uint32_t nl[E], nh[E];
-    if constexpr (PF)
-        if (blockIdx.x < tasks) load_task(blockIdx.x, nl, nh);
     for (uint32_t task = blockIdx.x; task < tasks; task += gridDim.x) {
         const uint32_t q = task / p.chunks;
         const uint32_t lo = lane_off(task);
         const uint64_t rel = cw_rel(p.cs, q);
         uint32_t l[E], h[E];
-        if constexpr (PF) {
-            sfor<E>([&](auto I) {
-                l[decltype(I)::value] = nl[decltype(I)::value];
-                h[decltype(I)::value] = nh[decltype(I)::value];
-            });
-            if (task + gridDim.x < tasks) load_task(task + gridDim.x, nl, nh);
-        } else {
-            load_task(task, l, h);
-        }
-        if constexpr (PIPE) grp_xform_pipe<E, false>(l, h, tI);
-        else grp_xform<E, false, JIT>(l, h, tI);
+        load_task(task, l, h);
+        grp_xform_pipe<E, false>(l, h, tI);
         {  // d = 16
             sfor<E / 2>([&](auto P) {
                 constexpr int i = 2 * decltype(P)::value;
@@ -1184,8 +819,7 @@ __global__ __launch_bounds__(1024, 4) void enc16h512_kernel(Enc16 p) {
                 swap_halves(h[i], h[i + 1]);
             });
             uint32_t c[kTabW];
-            if constexpr (JIT) tab_load_jit(wI + w * kTabW, c);
-            else tab_load(wI + w * kTabW, c);
+            tab_load_jit(wI + w * kTabW, c);
             sfor<E / 2>([&](auto P) {
                 constexpr int i = 2 * decltype(P)::value;
                 ifft2v(l[i], h[i], l[i + 1], h[i + 1], c);
@@ -1217,17 +851,14 @@ __global__ __launch_bounds__(1024, 4) void enc16h512_kernel(Enc16 p) {
         };
         to_res(l);
         to_res(h);
-        if constexpr (PIPE) res_xform_pipe<R, false>(l, h, rtab);
-        else res_xform<R, R, false, true, JIT>(l, h, rtab);
-        res_mid<R, R>(l, h, p.mid);
-        if constexpr (PIPE) res_xform_pipe<R, true>(l, h, rtab);
-        else res_xform<R, R, true, true, JIT>(l, h, rtab);
+        res_xform_pipe<R, false>(l, h, rtab);
+        res_mid<R>(l, h, p.mid);
+        res_xform_pipe<R, true>(l, h, rtab);
         to_grp(l);
         to_grp(h);
         {  // d = 16, then back to the plain group arrangement
             uint32_t c[kTabW];
-            if constexpr (JIT) tab_load_jit(wF + w * kTabW, c);
-            else tab_load(wF + w * kTabW, c);
+            tab_load_jit(wF + w * kTabW, c);
             sfor<E / 2>([&](auto P) {
                 constexpr int i = 2 * decltype(P)::value;
                 fft2v(l[i], h[i], l[i + 1], h[i + 1], c);
@@ -1238,13 +869,12 @@ __global__ __launch_bounds__(1024, 4) void enc16h512_kernel(Enc16 p) {
                 swap_halves(h[i], h[i + 1]);
             });
         }
-        if constexpr (PIPE) grp_xform_pipe<E, true>(l, h, tF);
-        else grp_xform<E, true, JIT>(l, h, tF);
+        grp_xform_pipe<E, true>(l, h, tF);
         const auto out = rsrc(p.cs.out_base + rel);
         // the store offsets are recomputed here from opaque copies (the compiler would
         // otherwise keep the load phase's 16 per-lane offsets alive across the transform)
         uint32_t slo = lo, slim = lim;
-#ifndef RSM_ENC16_HOISTED_OFFSETS  // (diagnostic A/B builds: the round-5 hoisted offsets)
+#ifndef RSM_ENC16_HOISTED_OFFSETS  // (diagnostic A/B builds: the hoisted offsets)
         asm volatile("" : "+v"(slo), "+v"(slim));
 #endif
         sfor<E>([&](auto I) {
@@ -1266,9 +896,8 @@ struct Dec16 {
     Res r;
     const uint16_t* logwalsh;
     uint16_t* errs;     // [count][n]
-    uint8_t* scratch;   // [count][2][n][S] (the five-pass form)
     uint32_t q0, count, chunks;
-    const PermTab16* tw;  // skewperm (the single-pass form)
+    const PermTab16* tw;  // skewperm
     uint32_t diag;        // diagnostic builds: dec16h_kernel A/B bits (rsm_diag_set_dec16_mode), else 0
 };
 
@@ -1332,176 +961,11 @@ __global__ __launch_bounds__(M) void errloc16_kernel(Dec16 p) {
     for (uint32_t i = threadIdx.x; i < (uint32_t)N; i += M) p.errs[(uint64_t)q * N + i] = (uint16_t)err[i];
 }
 
-__device__ __forceinline__ uint32_t err_of(const Dec16& p, uint32_t q, uint32_t i, uint32_t n) {
-    return __builtin_amdgcn_readfirstlane((uint32_t)p.errs[(uint64_t)q * n + i]);
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void dec16_p1(Dec16 p) {  // group: scale + IFFT low
-    constexpr int N = 2 * M;
-    const TaskIdx t = task_of(p.count, p.chunks, N / 16);
-    if (!t.valid) return;
-    const Lane ln = lane_of(t.chunk, p.ds.S);
-    const uint32_t k = p.ds.k, S = p.ds.S;
-    const auto sq = rsrc(p.ds.base);
-    const auto wk = rsrc(p.scratch + (uint64_t)t.q * 2 * N * S);
-    uint32_t l[16], h[16];
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t e = 16 * t.g + i;
-        uint32_t src = 0xFFFFFFFFu;  // share element feeding work slot e
-        if (e < k) src = k + e;                                 // recovery (parity)
-        else if (e >= (uint32_t)M && e < (uint32_t)M + k) src = e - M;  // original data
-        bool have = false;
-        uint32_t so = kOob16;
-        if (src != 0xFFFFFFFFu) {
-            const uint64_t cell = cell_of(p.ds, p.q0 + t.q, src);
-            have = p.ds.presence[cell] != 0;
-            if (have) so = (uint32_t)(cell * S);
-        }
-        have = __builtin_amdgcn_readfirstlane(have ? 1u : 0u) != 0;
-        l[i] = ld(sq, ln.lo, so);
-        h[i] = ld(sq, ln.lo + 32, so);
-        if (have) mul16(l[i], h[i], p.r.perm[err_of(p, t.q, e, N)]);
-    });
-    group_ifft(l, h, t.g, -1, p.r);
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t so = (16 * t.g + i) * S;
-        st(wk, l[i], ln.lo, so);
-        st(wk, h[i], ln.lo + 32, so);
-    });
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void dec16_p2(Dec16 p) {  // residue: IFFT high, H(in)
-    constexpr int N = 2 * M, R = N / 16;
-    const TaskIdx t = task_of(p.count, p.chunks, 16);
-    if (!t.valid) return;
-    const Lane ln = lane_of(t.chunk, p.ds.S);
-    const uint32_t S = p.ds.S;
-    const auto wk = rsrc(p.scratch + (uint64_t)t.q * 2 * N * S);
-    const uint32_t hoff = N * S;  // second array: H(in)
-    uint32_t l[R], h[R];
-    sfor<R>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const uint32_t so = (t.g + 16 * j) * S;
-        l[j] = ld(wk, ln.lo, so);
-        h[j] = ld(wk, ln.lo + 32, so);
-    });
-    residue_ifft<R>(l, h, -1, p.r);
-    sfor<R>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const uint32_t so = (t.g + 16 * j) * S;
-        st(wk, l[j], ln.lo, so);
-        st(wk, h[j], ln.lo + 32, so);
-        // high-bit half of the formal derivative, H(in)[j] (residue coordinate)
-        uint32_t al = 0, ah = 0;
-        sfor<12>([&](auto T) {
-            constexpr int tb = decltype(T)::value;
-            if constexpr ((1 << tb) < R && ((j >> tb) & 1) == 0 && j + (1 << tb) < R) {
-                al ^= l[j + (1 << tb)];
-                ah ^= h[j + (1 << tb)];
-            }
-        });
-        st(wk, al, ln.lo, hoff + so);
-        st(wk, ah, ln.lo + 32, hoff + so);
-    });
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void dec16_p3(Dec16 p) {  // group: out = in + L(in) + H(in)
-    constexpr int N = 2 * M;
-    const TaskIdx t = task_of(p.count, p.chunks, N / 16);
-    if (!t.valid) return;
-    const Lane ln = lane_of(t.chunk, p.ds.S);
-    const uint32_t S = p.ds.S;
-    const auto wk = rsrc(p.scratch + (uint64_t)t.q * 2 * N * S);
-    const uint32_t hoff = N * S;
-    uint32_t l[16], h[16], ol[16], oh[16];
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t so = (16 * t.g + i) * S;
-        l[i] = ld(wk, ln.lo, so);
-        h[i] = ld(wk, ln.lo + 32, so);
-    });
-    deriv_terms<16>(l, h, ol, oh);
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t so = (16 * t.g + i) * S;
-        const uint32_t hl = ld(wk, ln.lo, hoff + so), hh = ld(wk, ln.lo + 32, hoff + so);
-        st(wk, x3(l[i], ol[i], hl), ln.lo, so);
-        st(wk, x3(h[i], oh[i], hh), ln.lo + 32, so);
-    });
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void dec16_p4(Dec16 p) {  // residue: FFT high
-    constexpr int N = 2 * M, R = N / 16;
-    const TaskIdx t = task_of(p.count, p.chunks, 16);
-    if (!t.valid) return;
-    const Lane ln = lane_of(t.chunk, p.ds.S);
-    const uint32_t S = p.ds.S;
-    const auto wk = rsrc(p.scratch + (uint64_t)t.q * 2 * N * S);
-    uint32_t l[R], h[R];
-    sfor<R>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const uint32_t so = (t.g + 16 * j) * S;
-        l[j] = ld(wk, ln.lo, so);
-        h[j] = ld(wk, ln.lo + 32, so);
-    });
-    residue_fft<R>(l, h, p.r);
-    sfor<R>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const uint32_t so = (t.g + 16 * j) * S;
-        st(wk, l[j], ln.lo, so);
-        st(wk, h[j], ln.lo + 32, so);
-    });
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void dec16_p5(Dec16 p) {  // group: FFT low + reveal erasures
-    constexpr int N = 2 * M;
-    const TaskIdx t = task_of(p.count, p.chunks, N / 16);
-    if (!t.valid) return;
-    const Lane ln = lane_of(t.chunk, p.ds.S);
-    const uint32_t k = p.ds.k, S = p.ds.S;
-    const auto sq = rsrc(p.ds.base);
-    const auto wk = rsrc(p.scratch + (uint64_t)t.q * 2 * N * S);
-    uint32_t l[16], h[16];
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t so = (16 * t.g + i) * S;
-        l[i] = ld(wk, ln.lo, so);
-        h[i] = ld(wk, ln.lo + 32, so);
-    });
-    group_fft(l, h, t.g, p.r);
-    sfor<16>([&](auto E) {
-        constexpr int i = decltype(E)::value;
-        const uint32_t e = 16 * t.g + i;
-        uint32_t dst = 0xFFFFFFFFu;
-        if (e < k) dst = k + e;
-        else if (e >= (uint32_t)M && e < (uint32_t)M + k) dst = e - M;
-        if (dst != 0xFFFFFFFFu) {
-            const uint64_t cell = cell_of(p.ds, p.q0 + t.q, dst);
-            const bool missing = __builtin_amdgcn_readfirstlane(p.ds.presence[cell] ? 0u : 1u) != 0;
-            if (missing) {
-                const uint32_t L = kMod16 - err_of(p, t.q, e, N);
-                mul16(l[i], h[i], p.r.perm[L]);
-                const uint32_t so = (uint32_t)(cell * S);
-                st(sq, l[i], ln.lo, so);
-                st(sq, h[i], ln.lo + 32, so);
-            }
-        }
-    });
-}
-
-
 // ---------------------------------------------------------------------------
 // Single-pass decoder for m = 256 (n = 512 points; 129 <= k <= 256): one workgroup
 // of 16 waves per (codeword, 512-byte chunk) keeps the whole n-point transform on
-// chip, as enc16_kernel<512> does for the encoder -- the work array of the five
-// passes above never touches memory:
+// chip, wave w holding 32 elements of the chunk in registers (five passes through a
+// global work array were 1.3x slower: DESIGN.md, profiles/r04w_gf16_dec_ab.jsonl):
 //   group layout   (wave w: elements 32 w .. 32 w + 31): scale by the error locator,
 //                  IFFT layers d = 1..16;
 //   residue layout (wave w: residues 2 w, 2 w + 1; elements r + 32 j, j < 16): IFFT
@@ -1625,7 +1089,7 @@ __device__ __forceinline__ void deriv_plane(uint32_t (&v)[E], uint32_t (*xch)[64
 }
 
 // Twiddle tables staged once per workgroup in LDS and read by uniform ds_read_b128
-// (enc16_kernel<256>'s scheme; a scalar table load from L2 per butterfly block left
+// (as the encoders do; a scalar table load from L2 per butterfly block left
 // the 16-wave kernels waiting, ~6.6 cycles per VALU instruction): the exchange
 // buffer is half the elements (two passes per plane) so the tables fit beside it.
 // ZC: the zero-copy form for Repair (DecodeSet in_base / mirror: present cells read
@@ -1717,19 +1181,19 @@ __global__ __launch_bounds__(1024, 4) void dec16f_kernel(Dec16 p) {
         }
     });
     __syncthreads();  // the exchange buffer is free again
-    grp_xform<E, false, true>(l, h, gI + w * (E - 1) * kTabW);
+    grp_xform<E, false>(l, h, gI + w * (E - 1) * kTabW);
     xch_plane_half<E, R, true>(l, xch, w, lane);
     xch_plane_half<E, R, true>(h, xch, w, lane);
-    res_xform<E, R, false, false, true, true>(l, h, rtab);
+    res_xform<E, R, false, true>(l, h, rtab);
     deriv_plane<E, R>(l, xch, w, lane);
     deriv_plane<E, R>(h, xch, w, lane);
-    res_xform<E, R, true, false, true, true>(l, h, rtab);
+    res_xform<E, R, true, true>(l, h, rtab);
     xch_plane_half<E, R, false>(l, xch, w, lane);
     xch_plane_half<E, R, false>(h, xch, w, lane);
     uint32_t qr = q;
     asm volatile("" : "+s"(qr));
     stage_elem_tabs<N, 1024>(etab, p, qr, true);  // (the exchange's last barrier freed xch)
-    grp_xform<E, true, true>(l, h, gF + w * (E - 1) * kTabW);
+    grp_xform<E, true>(l, h, gF + w * (E - 1) * kTabW);
     __syncthreads();  // reveal tables staged
     sfor<E>([&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -1756,8 +1220,8 @@ __global__ __launch_bounds__(1024, 4) void dec16f_kernel(Dec16 p) {
 }
 
 // ---------------------------------------------------------------------------
-// Half-wave single-pass decoder for m = 512 (n = 1024 points; 257 <= k <= 512), round
-// 4: one workgroup of 16 waves per (codeword, 256-byte chunk); lane-half g = 2 w +
+// Half-wave single-pass decoder for m = 512 (n = 1024 points; 257 <= k <= 512):
+// one workgroup of 16 waves per (codeword, 256-byte chunk); lane-half g = 2 w +
 // (lane >> 5) of wave w holds ONE element's 256-byte chunk per register (32 lanes x 4
 // symbols), so the n-point state is 64 registers per lane, as in dec16f_kernel<256>:
 //   group layout   (half g: elements 32 g .. 32 g + 31): scale by exp(err), IFFT
@@ -1968,20 +1432,20 @@ __global__ __launch_bounds__(1024, 4) void dec16h_kernel(Dec16 p) {
     stage_res<R, E, 1024>(rtab, p.tw, -1);
     __syncthreads();  // twiddle tables staged
     d16_stamp(p, 3);
-    grp_xform<E, false, true>(l, h, gtab + g * (E - 1) * kTabW);
+    grp_xform<E, false>(l, h, gtab + g * (E - 1) * kTabW);
     d16_stamp(p, 4);
     xch_lanesplit<E>(l, xch, g, l32, true);
     xch_lanesplit<E>(h, xch, g, l32, true);
     // (the decoder's FFT twiddles SKEW[b + d - 1] are its IFFT ones SKEW[-1 + b + d]: the
     // group tables stay)
     d16_stamp(p, 5);
-    res_xform<E, R, false, false, true, false>(l, h, rtab);
+    res_xform<E, R, false, false>(l, h, rtab);
     d16_stamp(p, 6);
     uint32_t (*x2)[32] = reinterpret_cast<uint32_t (*)[32]>(&xch[0][0]);  // [N/2][32], the same 64 KiB
     deriv_halfwave<E, R>(l, x2, w, g, hi, l32);
     deriv_halfwave<E, R>(h, x2, w, g, hi, l32);
     d16_stamp(p, 7);
-    res_xform<E, R, true, false, true, false>(l, h, rtab);
+    res_xform<E, R, true, false>(l, h, rtab);
     d16_stamp(p, 8);
     xch_lanesplit<E>(l, xch, g, l32, false);
     xch_lanesplit<E>(h, xch, g, l32, false);
@@ -1996,7 +1460,7 @@ __global__ __launch_bounds__(1024, 4) void dec16h_kernel(Dec16 p) {
     if (!(p.diag & 1u))
 #endif
     if constexpr (PR) load_elem_tabs<N, 1024>(p, qr, true, rv);
-    grp_xform<E, true, true>(l, h, gtab + g * (E - 1) * kTabW);
+    grp_xform<E, true>(l, h, gtab + g * (E - 1) * kTabW);
     __syncthreads();  // every wave is past the twiddle tables
     d16_stamp(p, 10);
 #ifdef RSM_DIAG
@@ -2261,22 +1725,12 @@ __global__ __launch_bounds__(1024) void errloc16g_kernel(G16Pass p) {
 
 inline uint32_t blocks_for(uint64_t tasks) { return (uint32_t)((tasks + 3) / 4); }
 
-// m = 512 encoder form: 16 waves x 32 elements (production) or 8 x 64 (diagnostic A/B)
-// (diagnostic A/B: rsm_diag_set_enc16_e64 1 = 8 waves x 64 elements, 2 = the
-// round-3 16-wave form with scalar-loaded tables, one workgroup per task, 3 = that
-// form with the half exchange buffer, 5 = production with just-in-time table reads)
-#ifdef RSM_DIAG
-static std::atomic<int> g_enc16_e64{0};
-static bool enc16_e64() { return g_enc16_e64.load() == 1; }
-static int enc16_form() { return g_enc16_e64.load(); }
-#else
-static bool enc16_e64() { return false; }
-static int enc16_form() { return 0; }
-#endif
-
+// m = 256 / 512 encode: the half-wave kernels over (codeword, 256-byte chunk) tasks, a
+// persistent grid of as many workgroups as fit the device at once (m = 256: two per
+// CU, m = 512: one); SH = 1 / 2 for the multi-GPU all-to-all's hooks.
 template <int M>
 hipError_t run_encode(const CodewordSet& cs, const Gf16Dev& g, hipStream_t st) {
-    const uint32_t chunks = (cs.S + 511) / 512;
+    const uint32_t chunks = (cs.S + 255) / 256;
     const uint64_t tasks = (uint64_t)cs.count * chunks;
     if (tasks == 0) return hipSuccess;
     if (tasks >= (1ull << 31)) return hipErrorInvalidValue;
@@ -2284,193 +1738,56 @@ hipError_t run_encode(const CodewordSet& cs, const Gf16Dev& g, hipStream_t st) {
     const Gf16Host& hst = gf16_host();
     auto elem = [&](uint32_t L) { return L == kMod16 ? 0u : (uint32_t)hst.exp[L]; };
     const uint32_t sum = elem(hst.skew[M - 1 + M / 2]) ^ elem(hst.skew[M / 2 - 1]);
-    Enc16 p{cs, g.skewperm, chunks, sum ? g.perm + hst.log[sum] : nullptr};
-    // persistent forms: one workgroup per CU (two for the m = 256 half-wave form), the
-    // twiddle tables staged once per workgroup; the non-persistent diagnostic forms run
-    // one workgroup per task
-    const uint32_t pgrid = tasks > g.cus ? g.cus : (uint32_t)tasks;  // persistent forms
-    const uint32_t grid = M == 256 ? pgrid : (uint32_t)tasks;
-    if (cs.side || cs.blk) {  // multi-GPU all-to-all hooks: the production form with SH = 1 / 2
-        Enc16 ph = p;
-        ph.chunks = (cs.S + 255) / 256;
-        const uint64_t th = (uint64_t)cs.count * ph.chunks;
-        if (th >= (1ull << 31)) return hipErrorInvalidValue;
-        const uint32_t per_cu = M == 256 ? 2u : 1u;  // workgroups per CU of the half-wave forms
-        const uint32_t gh = th > (uint64_t)per_cu * g.cus ? per_cu * g.cus : (uint32_t)th;
-        if constexpr (M == 512) {
-            if (cs.side) hipLaunchKernelGGL((enc16h512_kernel<true, false, true, 1>), dim3(gh), dim3(1024), 0, st, ph);
-            else hipLaunchKernelGGL((enc16h512_kernel<true, false, true, 2>), dim3(gh), dim3(1024), 0, st, ph);
-        } else {
-            if (cs.side) hipLaunchKernelGGL((enc16h_kernel<true, false, true, 1>), dim3(gh), dim3(512), 0, st, ph);
-            else hipLaunchKernelGGL((enc16h_kernel<true, false, true, 2>), dim3(gh), dim3(512), 0, st, ph);
-        }
-        return hipGetLastError();
-    }
-    if constexpr (M == 512) {
-        if (enc16_e64()) {
-            hipLaunchKernelGGL((enc16_kernel<512, 64>), dim3(grid), dim3(512), 0, st, p);
-            return hipGetLastError();
-        }
-        // production since round 4 (form 0): the half-wave form with just-in-time tables
-        // (enc16h512_kernel<true>), c5 0.472-0.474 ms per square against 0.587-0.590 for
-        // 512-byte chunks (form 4 below; profiles/r04aa_gf16_enc_ab.jsonl).  Diagnostic
-        // forms: 1 8 waves x 64 elements (above), 4 persistent 16 waves x 32 elements, LDS
-        // tables beside a half exchange buffer (0.568-0.574, production through the
-        // round's middle), 2 the round-3 form (0.581-0.583), 3 form 2 with the half
-        // buffer, 5 form 4 with just-in-time table reads (0.584), 8 / 9 forms 4 / 5 with
-        // the merged middle pair, 16 the half-wave form with compiler-scheduled table
-        // reads (0.505-0.510)
-        switch (enc16_form()) {
-            case 0:      // production since round 6: the half-wave form with tables read one
-            case 21: {   // block ahead (form 21 in round 6's A/B: c5 0.451-0.466 against
-                         // 0.466-0.469 ms for just-in-time tables, now form 22;
-                         // profiles/r06i_gf16_pipe_ab.jsonl)
-                Enc16 ph = p;
-                ph.chunks = (cs.S + 255) / 256;
-                const uint64_t th = (uint64_t)cs.count * ph.chunks;
-                if (th >= (1ull << 31)) return hipErrorInvalidValue;
-                const uint32_t gh = th > g.cus ? g.cus : (uint32_t)th;
-                hipLaunchKernelGGL((enc16h512_kernel<true, false, true>), dim3(gh), dim3(1024), 0, st, ph);
-                return hipGetLastError();
-            }
-            case 22: {  // the round-4/5 production form: just-in-time table reads
-                Enc16 ph = p;
-                ph.chunks = (cs.S + 255) / 256;
-                const uint64_t th = (uint64_t)cs.count * ph.chunks;
-                if (th >= (1ull << 31)) return hipErrorInvalidValue;
-                const uint32_t gh = th > g.cus ? g.cus : (uint32_t)th;
-                hipLaunchKernelGGL(enc16h512_kernel<true>, dim3(gh), dim3(1024), 0, st, ph);
-                return hipGetLastError();
-            }
-            case 4: hipLaunchKernelGGL((enc16_kernel<512, 32, 3>), dim3(pgrid), dim3(1024), 0, st, p); return hipGetLastError();
-            case 3: hipLaunchKernelGGL((enc16_kernel<512, 32, 1>), dim3(grid), dim3(1024), 0, st, p); return hipGetLastError();
-            case 5: hipLaunchKernelGGL((enc16_kernel<512, 32, 7>), dim3(pgrid), dim3(1024), 0, st, p); return hipGetLastError();
-            case 8: hipLaunchKernelGGL((enc16_kernel<512, 32, 11>), dim3(pgrid), dim3(1024), 0, st, p); return hipGetLastError();
-            case 9: hipLaunchKernelGGL((enc16_kernel<512, 32, 15>), dim3(pgrid), dim3(1024), 0, st, p); return hipGetLastError();
-            case 18: {  // the production form with the next task's points prefetched
-                Enc16 ph = p;
-                ph.chunks = (cs.S + 255) / 256;
-                const uint64_t th = (uint64_t)cs.count * ph.chunks;
-                if (th >= (1ull << 31)) return hipErrorInvalidValue;
-                const uint32_t gh = th > g.cus ? g.cus : (uint32_t)th;
-                hipLaunchKernelGGL((enc16h512_kernel<true, true>), dim3(gh), dim3(1024), 0, st, ph);
-                return hipGetLastError();
-            }
-            case 16: {
-                Enc16 ph = p;
-                ph.chunks = (cs.S + 255) / 256;
-                const uint64_t th = (uint64_t)cs.count * ph.chunks;
-                if (th >= (1ull << 31)) return hipErrorInvalidValue;
-                const uint32_t gh = th > g.cus ? g.cus : (uint32_t)th;
-                hipLaunchKernelGGL(enc16h512_kernel<false>, dim3(gh), dim3(1024), 0, st, ph);
-                return hipGetLastError();
-            }
-            default: break;
-        }
-    }
-    if constexpr (M == 256) {
-        // production since round 4: the half-wave form (enc16h_kernel<true>: 256-byte
-        // chunks, 32 state registers, two workgroups per CU, just-in-time tables), c4
-        // 0.415-0.419 ms per square against 0.427-0.431 for 16 waves x 16 elements over
-        // 512-byte chunks (diagnostic form 6) and 0.435-0.450 for 8 waves x 32 elements
-        // (form 7, through round 3); form 14: the half-wave form with compiler-scheduled
-        // table reads (0.436-0.440).  profiles/r04k_gf16_enc_ab.jsonl, r04q_gf16_enc_ab.jsonl
-        const int form = enc16_form();
-        if (form == 6) {
-            hipLaunchKernelGGL((enc16_kernel<256, 16>), dim3(grid), dim3(1024), 0, st, p);
-            return hipGetLastError();
-        }
-        if (form != 7) {
-            Enc16 ph = p;
-            ph.chunks = (cs.S + 255) / 256;
-            const uint64_t th = (uint64_t)cs.count * ph.chunks;
-            if (th >= (1ull << 31)) return hipErrorInvalidValue;
-            const uint32_t gh = th > 2ull * g.cus ? 2u * g.cus : (uint32_t)th;
-            const uint32_t gh3 = th > 3ull * g.cus ? 3u * g.cus : (uint32_t)th;
-            if (form == 20) hipLaunchKernelGGL(enc16h3_kernel, dim3(gh3), dim3(512), 0, st, ph);
-            else if (form == 19) hipLaunchKernelGGL((enc16h_kernel<true, true>), dim3(gh), dim3(512), 0, st, ph);
-            else if (form == 14) hipLaunchKernelGGL(enc16h_kernel<false>, dim3(gh), dim3(512), 0, st, ph);
-            else if (form == 22) hipLaunchKernelGGL(enc16h_kernel<true>, dim3(gh), dim3(512), 0, st, ph);
-            // production since round 6 (and form 21): tables read one block ahead; c4
-            // 0.400-0.410 against 0.409-0.422 ms for just-in-time tables (form 22,
-            // profiles/r06i_gf16_pipe_ab.jsonl)
-            else hipLaunchKernelGGL((enc16h_kernel<true, false, true>), dim3(gh), dim3(512), 0, st, ph);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL(enc16_kernel<M>, dim3(grid), dim3(M * 2), 0, st, p);
+    const Enc16 p{cs, g.skewperm, chunks, sum ? g.perm + hst.log[sum] : nullptr};
+    constexpr uint32_t kThreads = M == 256 ? 512u : 1024u, kPerCu = M == 256 ? 2u : 1u;
+    const uint32_t grid = tasks > (uint64_t)kPerCu * g.cus ? kPerCu * g.cus : (uint32_t)tasks;
+    auto launch = [&](auto sh) {
+        constexpr int SH = decltype(sh)::value;
+        if constexpr (M == 256) hipLaunchKernelGGL(enc16h_kernel<SH>, dim3(grid), dim3(kThreads), 0, st, p);
+        else hipLaunchKernelGGL(enc16h512_kernel<SH>, dim3(grid), dim3(kThreads), 0, st, p);
+    };
+    if (cs.side) launch(std::integral_constant<int, 1>{});
+    else if (cs.blk) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 0>{});
     return hipGetLastError();
 }
 
 #ifdef RSM_DIAG
-static std::atomic<bool> g_dec16_five{false};
-static bool dec16_five_pass() { return g_dec16_five.load(); }
 static std::atomic<uint32_t> g_dec16_mode{0};
 static uint32_t dec16_diag_mode() { return g_dec16_mode.load(); }
 #else
-static bool dec16_five_pass() { return false; }
 static uint32_t dec16_diag_mode() { return 0u; }
 #endif
-// m = 512: the half-wave single pass (dec16h_kernel) since round 4 -- decode sweep
-// k = 512 1.43-1.45 ms against 1.84-1.85 for the five passes (diagnostic A/B:
-// rsm_diag_set_dec16_five_pass; profiles/r04w_gf16_dec_ab.jsonl)
-static bool dec16h_enabled() { return !dec16_five_pass(); }
-}  // namespace
-bool dec16_needs_work() { return dec16_five_pass(); }
-namespace {
 
-
+// m = 256 / 512 decode: the error locators of a batch of codewords (the host sizes
+// g.errs for the whole set), then the single-pass kernel -- m = 256: dec16f_kernel over
+// 512-byte chunks on a persistent grid; m = 512: dec16h_kernel, one workgroup per
+// (codeword, 256-byte chunk).  ZC when the present cells come from host-mapped memory.
 template <int M>
 hipError_t run_decode(const DecodeSet& ds, const Gf16Dev& g, const uint16_t* logwalsh, hipStream_t st) {
     constexpr int N = 2 * M;
-    const uint32_t chunks = (ds.S + 511) / 512;
-    // batches: the error locators of a batch (the host sizes them for the whole set);
-    // only the five-pass diagnostic form also needs per-codeword work arrays
-    uint32_t batch = (uint32_t)(g.errs_bytes / (N * sizeof(uint16_t)));
-    if (dec16_needs_work()) {
-        const uint32_t wbatch = (uint32_t)(g.scratch_bytes / (2ull * N * ds.S));
-        if (wbatch < batch) batch = wbatch;
-    }
+    const uint32_t chunks = M == 256 ? (ds.S + 511) / 512 : (ds.S + 255) / 256;
+    const uint32_t batch = (uint32_t)(g.errs_bytes / (N * sizeof(uint16_t)));
     if (batch == 0) return hipErrorOutOfMemory;
-    if ((ds.in_base || ds.mirror) && dec16_five_pass()) return hipErrorInvalidValue;  // no zero-copy five passes
     for (uint32_t q0 = 0; q0 < ds.count; q0 += batch) {
-        Dec16 p{ds, Res{g.perm, g.skew}, logwalsh, g.errs, g.scratch, q0,
-                ds.count - q0 < batch ? ds.count - q0 : batch, chunks, g.skewperm};
+        Dec16 p{ds, Res{g.perm, g.skew}, logwalsh, g.errs, q0, ds.count - q0 < batch ? ds.count - q0 : batch,
+                chunks, g.skewperm};
         p.ds.trace = dec_diag_trace_ptr();
         p.diag = dec16_diag_mode();
         hipLaunchKernelGGL(errloc16_kernel<M>, dim3(p.count), dim3(M), 0, st, p);
-        if constexpr (M == 512) {
-            if (dec16h_enabled()) {  // the half-wave single pass: 256-byte chunks
-                const uint32_t ch = (ds.S + 255) / 256;
-                Dec16 ph = p;
-                ph.chunks = ch;
-                if (ds.in_base) hipLaunchKernelGGL((dec16h_kernel<M, true>), dim3(p.count * ch), dim3(1024), 0, st, ph);
-                else hipLaunchKernelGGL((dec16h_kernel<M, false>), dim3(p.count * ch), dim3(1024), 0, st, ph);
-                if (hipError_t e = hipGetLastError()) return e;
-                continue;
-            }
-        }
+        const uint32_t tasks = p.count * chunks;
         if constexpr (M == 256) {
-            if (!dec16_five_pass()) {  // the single-pass form (diagnostic builds can A/B the five passes)
-                const uint32_t tk = p.count * chunks;
-                const uint32_t grid = tk > g.cus ? g.cus : tk;
-                if (ds.in_base) hipLaunchKernelGGL((dec16f_kernel<M, true>), dim3(grid), dim3(1024), 0, st, p);
-                else hipLaunchKernelGGL((dec16f_kernel<M, false>), dim3(grid), dim3(1024), 0, st, p);
-                if (hipError_t e = hipGetLastError()) return e;
-                continue;
-            }
+            const uint32_t grid = tasks > g.cus ? g.cus : tasks;
+            if (ds.in_base) hipLaunchKernelGGL((dec16f_kernel<M, true>), dim3(grid), dim3(1024), 0, st, p);
+            else hipLaunchKernelGGL((dec16f_kernel<M, false>), dim3(grid), dim3(1024), 0, st, p);
+        } else {
+            if (ds.in_base) hipLaunchKernelGGL((dec16h_kernel<M, true>), dim3(tasks), dim3(1024), 0, st, p);
+            else hipLaunchKernelGGL((dec16h_kernel<M, false>), dim3(tasks), dim3(1024), 0, st, p);
         }
-        hipLaunchKernelGGL(dec16_p1<M>, dim3(blocks_for((uint64_t)p.count * chunks * (N / 16))), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(dec16_p2<M>, dim3(blocks_for((uint64_t)p.count * chunks * 16)), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(dec16_p3<M>, dim3(blocks_for((uint64_t)p.count * chunks * (N / 16))), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(dec16_p4<M>, dim3(blocks_for((uint64_t)p.count * chunks * 16)), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(dec16_p5<M>, dim3(blocks_for((uint64_t)p.count * chunks * (N / 16))), dim3(256), 0, st, p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        if (hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;
 }
-
 
 // ---- generic multi-pass launchers (m >= 1024) ----
 template <int BITS, int NI, int NF>
@@ -2656,8 +1973,6 @@ static hipError_t run_decode_generic(const DecodeSet& ds0, const Gf16Dev& g, hip
 }  // namespace
 
 #ifdef RSM_DIAG
-void set_enc16_diag_e64(int mode) { g_enc16_e64.store(mode); }
-void set_dec16_diag_five_pass(bool on) { g_dec16_five.store(on); }
 void set_dec16_diag_mode(uint32_t m) { g_dec16_mode.store(m); }
 #endif
 

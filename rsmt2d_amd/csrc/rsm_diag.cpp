@@ -69,16 +69,6 @@ int rsm_diag_set_split_fused(int on) {
     return RSM_OK;
 }
 
-int rsm_diag_set_enc16_e64(int mode) {
-    set_enc16_diag_e64(mode);
-    return RSM_OK;
-}
-
-int rsm_diag_set_dec16_five_pass(int on) {
-    set_dec16_diag_five_pass(on != 0);
-    return RSM_OK;
-}
-
 int rsm_diag_set_dec_trace(void* d_trace) {
     set_dec_diag_trace(static_cast<uint32_t*>(d_trace));
     return RSM_OK;

@@ -126,9 +126,6 @@ hipError_t launch_encode_gf8(const CodewordSet& cs, hipStream_t st);
 // bases, a capped grid looping over the (codeword, 256-byte chunk) tasks
 hipError_t launch_encode_gf8_wide(const CodewordSet& cs, hipStream_t st);
 hipError_t launch_decode_gf8_wide(const DecodeSet& ds, hipStream_t st);
-// whether the GF(2^16) m <= 512 decoder in use needs per-stream work arrays (only the
-// five-pass diagnostic form does; the single-pass forms keep everything on chip)
-bool dec16_needs_work();
 // bit-sliced M = 128 encode (kernels_gf8_bs.hip); launch_encode_gf8 picks it when applicable
 bool bs128_applicable(const CodewordSet& cs);
 hipError_t launch_encode_gf8_bs128(const CodewordSet& cs, hipStream_t st);
@@ -143,8 +140,6 @@ constexpr int kSplitWavesOne = 16;  // one square / one codeword: the 16-wave la
 constexpr uint32_t kSplitSmallBatch = 64;  // 9 <= k <= 64: squares per call for the split form (split_max > 0)
 void set_split_diag_waves(int first, int second);  // diagnostic builds only
 void set_split_diag_fused(bool on);                  // diagnostic builds only
-void set_enc16_diag_e64(int mode);                   // diagnostic builds only
-void set_dec16_diag_five_pass(bool on);              // diagnostic builds only
 void set_dec16_diag_mode(uint32_t mode);            // diagnostic builds only: dec16h_kernel A/B bits
 bool bs128_diag_xcd_queues();                        // diagnostic builds only: XCD-affine queue mode set
 bool split_fused_enabled();                          // product: always

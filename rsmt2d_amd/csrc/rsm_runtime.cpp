@@ -276,8 +276,6 @@ int launch_decode(rsm_ctx* ctx, const DecodeSet& ds0, hipStream_t st) {
     // each half of a row / column (its k data or k parity cells) from its own base
     const uint64_t es = ds.axis == 0 ? (uint64_t)ds.S : 2ull * ds.k * ds.S;
     ds.wide = narrow_ok(ctx, ds.k, es, ds.S) ? 0u : 1u;
-    // (the five-pass diagnostic GF(2^16) form addresses the whole square with 32-bit offsets)
-    if (field_bits(ds.k) == 16 && dec16_needs_work() && 4ull * ds.k * ds.k * ds.S >= kOffsetLimit) ds.wide = 1u;
     if (ds.wide && (ds.in_base || ds.mirror))
         return fail(RSM_EUNSUPPORTED, "decode: zero-copy form of a codeword over the offset limit");
     if (ds.wide) ds.pitch = ds.S;
@@ -294,7 +292,7 @@ int launch_decode(rsm_ctx* ctx, const DecodeSet& ds0, hipStream_t st) {
         StreamScratch& ss = stream_scratch(ctx, st);
         std::lock_guard<std::mutex> lk(ss.mu);
         Gf16Dev g;
-        if (!gf16_generic(ds.k) && !ds.wide && !dec16_needs_work()) {
+        if (!gf16_generic(ds.k) && !ds.wide) {
             // single pass per codeword: only the error locators of every codeword
             if (int rc = gf16_for_stream(ctx, ss, st, 0, ds.count * n * sizeof(uint16_t), &g)) return rc;
         } else {

@@ -167,6 +167,19 @@ def test_product_has_no_diagnostics(lib):
     assert b"extend_gf8_bs128q_kernel" not in blob
     assert not any(int(m) & (6 | 32768) for m in modes | smodes)
     assert b"encode_gf8_bs128p_kernel" not in blob
+    # the GF(2^16) m = 256 / 512 kernels (kernels_gf16.hip): exactly the forms the product
+    # launches -- the half-wave encoders with SH = 0 (plain), 1 and 2 (the all-to-all's
+    # hooks), the single-pass decoders with and without zero-copy input, and the error
+    # locators; none of the forms that lost their A/B runs
+    k16 = {n + a for n, a in re.findall(
+        rb"_GLOBAL__N_1\d+((?:enc16|dec16|errloc16)[a-z0-9_]*)((?:I(?:L[ib]\d+E)+E)?)", blob)}
+    assert k16 == ({b"enc16h_kernelILi%dEE" % sh for sh in (0, 1, 2)}
+                   | {b"enc16h512_kernelILi%dEE" % sh for sh in (0, 1, 2)}
+                   | {b"dec16f_kernelILi256ELb%dEE" % zc for zc in (0, 1)}
+                   | {b"dec16h_kernelILi512ELb%dEE" % zc for zc in (0, 1)}
+                   | {b"errloc16_kernelILi256EE", b"errloc16_kernelILi512EE", b"errloc16g_kernel"}), k16
+    for name in (b"dec16_p1", b"enc16_kernel", b"enc16h3_kernel"):
+        assert name not in blob, name
     txt = re.sub(r"/\*.*?\*/", "", open(DIAG_HEADER).read(), flags=re.S)
     for s in set(re.findall(r"\b(rsm_diag_[a-z0-9_]+)\s*\(", txt)):
         assert not hasattr(lib, s), s

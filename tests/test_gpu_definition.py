@@ -108,9 +108,8 @@ def test_encode_gf8_m128(lib, k):
 @pytest.mark.parametrize("S", [64, 576])
 @pytest.mark.parametrize("k", [129, 256, 257, 512])
 def test_encode_gf16_single_pass(lib, k, S):
-    """GF(2^16), m = 256: enc16h_kernel<true, false, true>; m = 512:
-    enc16h512_kernel<true, false, true> (run_encode<M>, the production forms); S = 576 is
-    nine 64-byte blocks, so the last 256-byte chunk is partial."""
+    """GF(2^16), m = 256: enc16h_kernel<0>; m = 512: enc16h512_kernel<0> (run_encode<M>);
+    S = 576 is nine 64-byte blocks, so the last 256-byte chunk is partial."""
     _encode_case(k, S)
 
 

@@ -304,6 +304,30 @@ def test_repair_half_of_each_row(lib, rng, k):
     assert eds.repair_stats().fast_path == 1
 
 
+@pytest.mark.parametrize("k", [129, 257])
+def test_repair_half_of_each_row_gf16(lib, rng, k):
+    """The same scheme at the smallest m = 256 and m = 512 squares, 64-byte shares: the
+    zero-copy row sweep reads the present cells from the mapped host square
+    (errloc16_kernel + dec16f_kernel<256, true> / dec16h_kernel<512, true>); the repaired
+    square equals the oracle's extension bit for bit."""
+    S_ = 64
+    ods = rng.integers(0, 256, (k, k, S_), dtype=np.uint8)
+    want = oracle.extend_square(ods, nthreads=8)
+    w = 2 * k
+    original = R.ComputeExtendedDataSquare([ods[r, c].tobytes() for r in range(k) for c in range(k)],
+                                           R.NewLeoRSCodec(), R.NewDefaultTree)
+    rr, cr = _roots(original)
+    flat = [want[r, c].tobytes() for r in range(w) for c in range(w)]
+    assert original.Flattened() == flat
+    for r in range(w):
+        for c in rng.choice(w, size=k, replace=False):
+            flat[r * w + c] = None
+    eds = R.ImportExtendedDataSquare(flat, R.NewLeoRSCodec(), R.NewDefaultTree)
+    eds.Repair(rr, cr)
+    assert eds.Flattened() == [want[r, c].tobytes() for r in range(w) for c in range(w)]
+    assert eds.repair_stats().fast_path == 1
+
+
 def test_repair_half_of_each_row_byzantine_k128(lib, rng):
     """The zero-copy row sweep (k = 128, every row decodable) with one corrupted
     present share: the device verification rejects it, the EDS is left as it was
