@@ -17,6 +17,10 @@ extern "C" {
 /* Kernel variant of the bit-sliced GF(2^8) M = 128 encode, process-wide:
  * 40 = production; 0 / 8 / 24 / 56 = A-B variants (exchange form, cache policy);
  * 2 = no arithmetic, 4 = no global memory (both give WRONG output by design).
+ * Exchange store path of the half-split queue kernel (correct output): 58000 = 32-bit
+ * exchange stores (the round-5 body), 58001 = 32-bit stores + the tail of the large
+ * layers inside the exchange reads, 58002 = production (64-bit stores), 58003 = 64-bit
+ * stores + the tail inside the reads; 58030..58033 = the same with the phase timeline.
  * rev_col: column pass in reverse set order; xcd: bit 0 rows / bit 1 columns in
  * XCD-grouped set order. */
 int rsm_diag_set_bs_mode(int mode, int rev_col, int xcd);

@@ -55,6 +55,10 @@ RSM_BS8_DEV void mid2_asm(uint32_t (&x)[8], uint32_t (&y)[8]);
 #include "bs8_asm.inc"
 // small-layout layers of all eight waves, one asm statement each (branch on A inside)
 #include "bs8_small.inc"
+#ifdef RSM_DIAG
+// A/B forms of the half-split set body that only the diagnostic library launches
+#include "bs8_small_diag.inc"
+#endif
 #endif
 
 // Host reference: the same networks, interpreted from the generated table.

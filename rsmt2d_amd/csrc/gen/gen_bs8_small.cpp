@@ -417,18 +417,185 @@ static void emit_phase(const char* name, int W, int kind) {
     printf("\"v\"(va), \"v\"(vb) : \"memory\");\n}\n");
 }
 
+// ---------------------------------------------------------------------------
+// Store-path relief of the exchange ("exchange store path").
+// The windows of emit_phase that hold a large IFFT / FFT are bound by the LDS store
+// path (64 ds_write_b32 x 4 cycles x 8 waves = 2,048 cycles per CU against ~1,200
+// cycles of VALU), and every exchange read is a burst during which no VALU issues.
+// Two changes, each with its own generated forms so that they can be A/B-ed apart
+// (measured: change 2 is production, change 1 stays in the diagnostic build only):
+//   1. the END of the large layers (about the last layer's worth, kTailValu instructions)
+//      leaves the store window and runs inside the statement that reads the other half
+//      back (emit_read_tail): the window stays store-bound, the tail fills the read
+//      burst.  The three layers are optimized as ONE block (ir_optimize, as emit_phase
+//      does) and the optimized op list is cut at an op boundary, so no fold across
+//      layers is lost: head + tail are the parent's instructions in the parent's order;
+//   2. the stores are ds_write_b64 of the pair (X[v][2q], X[v][2q + 1]) -- the pair a
+//      reader's ds_read_b64 fills -- at lane * 8: 32 stores of 6 cycles instead of 64
+//      of 4, same entries, same bytes.
+// Operand numbering of these forms (pair operands and immediates cannot sit between
+// the outputs, so the %0..%127 = X numbering of emit_phase cannot be kept; the VALU
+// half keeps its numbers RELATIVE to the half, as emit_half does):
+//   %0..%63  X[8V + b][i] (operand 8b + i), V the half the VALU works on, "+v"
+//   %64..    the temporaries, then (read forms) the 32 pairs read, "=&v"
+//   then the transpose masks (SGPRs), the stored data (32 pairs T[v][q] = X[8W + v][2q],
+//   X[8W + v][2q + 1], or 64 singles X[8W + v][p], operand order v-major) and the two
+//   address registers.
+static std::vector<std::vector<Bfly>> large_layers(int kind, int V, int l0, int l1) {
+    const int kOffEnc = 127;
+    std::vector<std::vector<Bfly>> layers;
+    for (int li = l0; li < l1; ++li) {
+        const int dh = kind == 1 ? (1 << li) : (4 >> li);
+        std::vector<Bfly> l;
+        for (int bb = 0; bb < 8; bb += 2 * dh) {
+            const int hb = 8 * V + bb;
+            const unsigned L = kind == 1 ? kGf8.skew[kOffEnc + 8 * hb + 8 * dh] : kGf8.skew[-1 + 8 * hb + 8 * dh];
+            for (int q = 0; q < dh; ++q) l.push_back({kind == 1 ? 0 : 1, L, hb + q, hb + q + dh});
+        }
+        layers.push_back(l);
+    }
+    return layers;
+}
+static const int kTailValu = 80;  // most VALU instructions moved into an exchange read
+// part 0: the whole optimized block; 1: its head; 2: its tail (the longest run of whole
+// ops at the end with at most kTailValu instructions)
+static std::vector<IrOp> large_ir(int kind, int V, int part) {
+    const auto layers = large_layers(kind, V, 0, 3);
+    std::vector<IrOp> ir = block_ir(layers);
+    size_t cut = ir.size();
+    for (int n = 0; cut > 0; --cut) {
+        n += ir_count(std::vector<IrOp>{ir[cut - 1]});
+        if (n > kTailValu) break;
+    }
+    if (part == 1) ir.erase(ir.begin() + (long)cut, ir.end());
+    if (part == 2) ir.erase(ir.begin(), ir.begin() + (long)cut);
+    return ir;
+}
+// VALU instruction list with `other` (LDS instructions) spread evenly through it, the
+// first `lead` of them in front
+static void print_spread(const std::vector<std::string>& valu, const std::vector<std::string>& other, size_t lead) {
+    size_t w = 0;
+    for (; w < lead && w < other.size(); ++w) printf("        \"%s\\n\\t\"\n", other[w].c_str());
+    const size_t n = valu.size(), m = other.size() - w, w0 = w;
+    for (size_t i = 0; i < n; ++i) {
+        while (w < other.size() && (w - w0 + 1) * n / (m + 1) <= i) printf("        \"%s\\n\\t\"\n", other[w++].c_str());
+        printf("        \"%s\\n\\t\"\n", valu[i].c_str());
+    }
+    while (w < other.size()) printf("        \"%s\\n\\t\"\n", other[w++].c_str());
+}
+// Exchange writes of half W (b64: 32 ds_write_b64, else 64 ds_write_b32) spread through
+// VALU work on half V = 1 - W: kind 0 / 3 the transposes (as emit_phase), kind 1 / 2
+// the large IFFT / FFT of half V (part 0: all of it, 1: without the tail of large_ir).
+static void emit_phase_x(const char* name, int W, int kind, int part, bool b64) {
+    const int V = 1 - W;
+    std::vector<std::string> valu, wr;
+    std::vector<IrOp> ir;
+    if (kind == 1 || kind == 2) ir = large_ir(kind, V, part);
+    const int nt = (kind == 0 || kind == 3) ? 2 : std::max(1, ir_temps(ir));
+    const int nm = (kind == 0 || kind == 3) ? 3 : 0;
+    const int mk = 64 + nt, d0 = mk + nm, nd = b64 ? 32 : 64;
+    const int va = d0 + nd, vb = va + 1;
+    char b[96];
+    if (b64) {
+        for (int q = 0; q < 4; ++q)
+            for (int v = 0; v < 8; ++v) {
+                snprintf(b, sizeof b, "ds_write_b64 %%%d, %%%d offset:%d", q >= 2 ? vb : va, d0 + 4 * v + q, ((q % 2) * 8 + v) * 4096);
+                wr.push_back(b);
+            }
+    } else {
+        for (int p = 0; p < 8; ++p)
+            for (int v = 0; v < 8; ++v) {
+                snprintf(b, sizeof b, "ds_write_b32 %%%d, %%%d offset:%d", wr_hi(p) ? vb : va, d0 + 8 * v + p, wr_off(p, v));
+                wr.push_back(b);
+            }
+    }
+    if (kind == 0 || kind == 3) {
+        for (int j = 0; j < 8; ++j) {
+            const int w[8] = {8 * j, 8 * j + 1, 8 * j + 2, 8 * j + 3, 8 * j + 4, 8 * j + 5, 8 * j + 6, 8 * j + 7};
+            tp_ops(kind == 3, w, 64, 65, mk, mk + 1, mk + 2, valu);
+        }
+    } else {
+        ir_emit(ir, [V](int sym, int i) { return 8 * (sym - 8 * V) + i; }, 64, valu);
+    }
+    printf("RSM_BS8_DEV void %s(uint32_t (&X)[16][8], uint32_t va, uint32_t vb) {\n", name);
+    print_temps_decl(nt);
+    if (b64) {
+        printf("    uint64_t T[8][4];\n    for (int v = 0; v < 8; ++v)\n        for (int q = 0; q < 4; ++q)\n"
+               "            T[v][q] = (uint64_t)X[%d + v][2 * q] | ((uint64_t)X[%d + v][2 * q + 1] << 32);\n", 8 * W, 8 * W);
+    }
+    printf("    asm volatile(\n");
+    print_spread(valu, wr, 0);
+    printf("        \"s_nop 0\"\n        :");
+    for (int j = 8 * V; j < 8 * V + 8; ++j)
+        for (int i = 0; i < 8; ++i) printf(" \"+v\"(X[%d][%d]),", j, i);
+    print_temps_ops(nt);
+    printf("\n        : ");
+    if (nm == 3) printf("\"s\"(0xF0F0F0F0u), \"s\"(0xCCCCCCCCu), \"s\"(0xAAAAAAAAu), ");
+    for (int v = 0; v < 8; ++v)
+        for (int q = 0; q < nd / 8; ++q) {
+            if (b64) printf("\"v\"(T[%d][%d]), ", v, q);
+            else printf("\"v\"(X[%d][%d]), ", 8 * W + v, q);
+        }
+    printf("\"v\"(va), \"v\"(vb) : \"memory\");\n}\n");
+}
+// The exchange read of half G (entries as emit_xch) with the tail of the large IFFT /
+// FFT (kind 1 / 2) of the OTHER half in the same statement: kReadLead reads in front,
+// the rest spread through the VALU work, then lgkmcnt(0) -- the outputs are waited for
+// inside the statement, as in xch_read_hG.  The pairs read and the VALU registers are
+// disjoint.
+static const size_t kReadLead = 16;  // (a wave keeps at most 15 LDS operations in flight)
+static void emit_read_tail(const char* name, int G, int kind) {
+    const int V = 1 - G;
+    std::vector<IrOp> ir = large_ir(kind, V, 2);
+    const int nt = std::max(1, ir_temps(ir));
+    const int t0 = 64 + nt, ra = t0 + 32, rb = ra + 1;
+    std::vector<std::string> valu, rd;
+    ir_emit(ir, [V](int sym, int i) { return 8 * (sym - 8 * V) + i; }, 64, valu);
+    char b[96];
+    for (int q = 0; q < 4; ++q)
+        for (int u = 0; u < 8; ++u) {
+            snprintf(b, sizeof b, "ds_read_b64 %%%d, %%%d offset:%d", t0 + 4 * u + q, q < 2 ? ra : rb, (q % 2) * 32768 + u * 512);
+            rd.push_back(b);
+        }
+    printf("RSM_BS8_DEV void %s(uint32_t (&X)[16][8], uint32_t ra, uint32_t rb) {\n", name);
+    print_temps_decl(nt);
+    printf("    uint64_t T[8][4];\n    asm volatile(\n");
+    print_spread(valu, rd, kReadLead);
+    printf("        \"s_waitcnt lgkmcnt(0)\"\n        :");
+    for (int j = 8 * V; j < 8 * V + 8; ++j)
+        for (int i = 0; i < 8; ++i) printf(" \"+v\"(X[%d][%d]),", j, i);
+    print_temps_ops(nt);
+    printf(",");
+    for (int u = 0; u < 8; ++u)
+        for (int q = 0; q < 4; ++q) printf(" \"=&v\"(T[%d][%d])%s", u, q, (u == 7 && q == 3) ? "" : ",");
+    printf("\n        : \"v\"(ra), \"v\"(rb) : \"memory\");\n");
+    printf("    for (int u = 0; u < 8; ++u)\n        for (int q = 0; q < 4; ++q) {\n"
+           "            X[%d + u][2 * q] = (uint32_t)T[u][q];\n            X[%d + u][2 * q + 1] = (uint32_t)(T[u][q] >> 32);\n"
+           "        }\n}\n", 8 * G, 8 * G);
+}
 
-int main() {
+// usage: gen_bs8_small DIAG_FILE > bs8_small.inc   (DIAG_FILE = bs8_small_diag.inc: the
+// forms only the diagnostic library launches, apart from the four emit_phase blocks
+// that stay in bs8_small.inc under RSM_DIAG)
+int main(int argc, char** argv) {
+    if (argc != 2) {
+        fprintf(stderr, "usage: gen_bs8_small DIAG_FILE > bs8_small.inc\n");
+        return 2;
+    }
     printf("// GENERATED by gen/gen_bs8_small.cpp -- do not edit.\n");
     emit_xch(0);
     emit_xch(1);
-    emit_phase("ph_w0_tr1", 0, 0);    // S' -> L half 0  || transposes of h1 (bytes -> planes)
-    emit_phase("ph_w1_lifft0", 1, 1); // S' -> L half 1  || large IFFT of h0
-    emit_phase("ph_w0_lfft1", 0, 2);  // L -> S' half 0  || large FFT of h1
-    emit_phase("ph_w1_tr0", 1, 3);    // L -> S' half 1  || transposes of h0 (planes -> bytes)
+    // production: 64-bit exchange stores (change 2; change 1 showed no gain in its A/B)
+    emit_phase_x("ph_w0_tr1_w64", 0, 0, 0, true);       // S' -> L half 0  || transposes of h1 (bytes -> planes)
+    emit_phase_x("ph_w1_lifft0_w64", 1, 1, 0, true);    // S' -> L half 1  || large IFFT of h0
+    emit_phase_x("ph_w0_lfft1_w64", 0, 2, 0, true);     // L -> S' half 0  || large FFT of h1
+    emit_phase_x("ph_w1_tr0_w64", 1, 3, 0, true);       // L -> S' half 1  || transposes of h0 (planes -> bytes)
     printf("#ifdef RSM_DIAG\n");
-    emit_phase("ph_w0_tr1_old", 0, 4);
-    emit_phase("ph_w1_tr0_old", 1, 4);
+    // the 32-bit-store body (emit_phase) and the forms of change 1, for the A/B
+    emit_phase("ph_w0_tr1", 0, 0);
+    emit_phase("ph_w1_lifft0", 1, 1);
+    emit_phase("ph_w0_lfft1", 0, 2);
+    emit_phase("ph_w1_tr0", 1, 3);
     printf("#endif\n");
     emit_lmid("lmid_all");
     emit_tp("tp_fwd_dev", false);
@@ -439,6 +606,19 @@ int main() {
     emit_half("small_ifft_h1_all", true, 1);
     emit_half("small_fft_h0_all", false, 0);
     emit_half("small_fft_h1_all", false, 1);
+    if (!freopen(argv[1], "w", stdout)) {
+        perror(argv[1]);
+        return 1;
+    }
+    printf("// GENERATED by gen/gen_bs8_small.cpp -- do not edit.  Diagnostic build only.\n");
+    emit_phase_x("ph_w1_lifft0a", 1, 1, 1, false);      // S' -> L half 1  || large IFFT of h0, head; 32-bit stores
+    emit_phase_x("ph_w0_lfft1a", 0, 2, 1, false);       // L -> S' half 0  || large FFT of h1, head; 32-bit stores
+    emit_phase_x("ph_w1_lifft0a_w64", 1, 1, 1, true);   // the same with 64-bit stores
+    emit_phase_x("ph_w0_lfft1a_w64", 0, 2, 1, true);
+    emit_read_tail("xch_read_h1_lifft0b", 1, 1);        // read of h1      || large IFFT of h0, tail
+    emit_read_tail("xch_read_h0_lfft1b", 0, 2);         // read of h0      || large FFT of h1, tail
+    emit_phase("ph_w0_tr1_old", 0, 4);
+    emit_phase("ph_w1_tr0_old", 1, 4);
     fprintf(stderr, "half-split blocks: %ld VALU butterfly by butterfly, %ld optimized\n", g_plain, g_opt);
     return 0;
 }

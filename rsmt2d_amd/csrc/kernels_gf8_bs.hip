@@ -1035,6 +1035,15 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
     // 8388608: the round-3 shift-pair transposes (bs8.hpp transpose8_dev) instead of the
     // rotate-and-select network (gen_bs8_small.cpp tp_ops) -- A/B
     constexpr bool OLDTP = (MODE & 8388608) != 0;
+    // The exchange store path (gen_bs8_small.cpp emit_phase_x / emit_read_tail).  Production:
+    // the exchange stores are ds_write_b64 (32 per window instead of 64 ds_write_b32).
+    // Diagnostic build only, for the A/B: 536870912 = the ds_write_b32 stores of round 5;
+    // 268435456 = the tail of the large layers of P2 / P3 moved out of the store window
+    // into the statement that reads the other half back (measured: no gain, DESIGN.md
+    // section 8).
+#ifdef RSM_DIAG
+    constexpr bool TAIL = (MODE & 268435456) != 0, W64 = (MODE & 536870912) == 0 && !OLDTP;
+#endif
     auto tp_fwd = [](uint32_t (&w)[8]) {
         if constexpr (OLDTP) bs8::transpose8_dev(w);
         else bs8::tp_fwd_dev(w);
@@ -1204,9 +1213,10 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
             if constexpr (IL) {
 #ifdef RSM_DIAG
                 if constexpr (OLDTP) bs8::ph_w0_tr1_old(X, xw, xw + 65536u);
+                else if constexpr (!W64) bs8::ph_w0_tr1(X, xw, xw + 65536u);
                 else
 #endif
-                bs8::ph_w0_tr1(X, xw, xw + 65536u);
+                bs8::ph_w0_tr1_w64(X, xw, xw + 65536u);
                 bs8::small_ifft_h1_all(X, A);
             } else {
                 if constexpr (XCH) bs8::xch_write_h0(X, xw, xw + 65536u);
@@ -1224,13 +1234,26 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
             stamp(4);
             // ---- S' -> L, half 1 || large IFFT of h0 ----
             if constexpr (IL) {
-                bs8::ph_w1_lifft0(X, xw, xw + 65536u);
+#ifdef RSM_DIAG
+                if constexpr (!TAIL && !W64) bs8::ph_w1_lifft0(X, xw, xw + 65536u);
+                else if constexpr (TAIL && W64) bs8::ph_w1_lifft0a_w64(X, xw, xw + 65536u);  // the tail runs in the read below
+                else if constexpr (TAIL) bs8::ph_w1_lifft0a(X, xw, xw + 65536u);
+                else
+#endif
+                bs8::ph_w1_lifft0_w64(X, xw, xw + 65536u);
             } else {
                 if constexpr (XCH) bs8::xch_write_h1(X, xw, xw + 65536u);
                 if constexpr (ARITH) bs8::large_ifft_h<0>(X);
             }
+            // h1's stores are complete (lgkmcnt(0)) in every wave before this barrier; the
+            // read statement waits for its own data (lgkmcnt(0) inside), so every wave's
+            // reads of h1 are complete before the barrier that precedes P3's stores of h0
             RSM_LDS_SYNC;
             keep_half<1>(X);
+#ifdef RSM_DIAG
+            if constexpr (IL && TAIL) bs8::xch_read_h1_lifft0b(X, xr, xr + 65536u);  // + the tail of the large IFFT of h0
+            else
+#endif
             if constexpr (XCH) bs8::xch_read_h1(X, xr, xr + 65536u);
             asm volatile("s_barrier" ::: "memory");
             stamp(5);
@@ -1278,7 +1301,13 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
             stamp(7);
             // ---- L -> S', half 0 || large FFT of h1 ----
             if constexpr (IL) {
-                bs8::ph_w0_lfft1(X, xw, xw + 65536u);
+#ifdef RSM_DIAG
+                if constexpr (!TAIL && !W64) bs8::ph_w0_lfft1(X, xw, xw + 65536u);
+                else if constexpr (TAIL && W64) bs8::ph_w0_lfft1a_w64(X, xw, xw + 65536u);  // the tail runs in the read below
+                else if constexpr (TAIL) bs8::ph_w0_lfft1a(X, xw, xw + 65536u);
+                else
+#endif
+                bs8::ph_w0_lfft1_w64(X, xw, xw + 65536u);
             } else {
                 if constexpr (XCH) bs8::xch_write_h0(X, xw, xw + 65536u);
                 if constexpr (ARITH) bs8::large_fft_h<1>(X);
@@ -1313,8 +1342,14 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
                 slot[1] = nnsq;
                 slot[2] = r;
             }
+            // as after P2: stores of h0 complete before this barrier, reads of h0 complete
+            // (inside the statement) before the barrier that precedes P4's stores of h1
             RSM_LDS_SYNC;
             keep_half<0>(X);
+#ifdef RSM_DIAG
+            if constexpr (IL && TAIL) bs8::xch_read_h0_lfft1b(X, xr, xr + 65536u);  // + the tail of the large FFT of h1
+            else
+#endif
             if constexpr (XCH) bs8::xch_read_h0(X, xr, xr + 65536u);
             asm volatile("s_barrier" ::: "memory");
             stamp(8);
@@ -1327,9 +1362,10 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
                 bs8::small_fft_h0_all(X, A);
 #ifdef RSM_DIAG
                 if constexpr (OLDTP) bs8::ph_w1_tr0_old(X, xw, xw + 65536u);
+                else if constexpr (!W64) bs8::ph_w1_tr0(X, xw, xw + 65536u);
                 else
 #endif
-                bs8::ph_w1_tr0(X, xw, xw + 65536u);  // + planes -> bytes of h0
+                bs8::ph_w1_tr0_w64(X, xw, xw + 65536u);  // + planes -> bytes of h0
                 split_store_h<0, false, true, false, XCDQ, OPQ>(X, a, A, k, oo, es, crow != 0, MEM);
                 if constexpr (XLOAD) {
                     if (pre) {
@@ -1702,6 +1738,18 @@ hipError_t launch_extend_gf8_bs128_queue(const QueuePlan& p0, hipStream_t st) {
         case 51004: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<262148>), dim3(grid), dim3(512), 0, st, p); break;
         case 52040: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<4194304>), dim3(grid), dim3(512), 0, st, p); break;
         case 53000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<8388608>), dim3(grid), dim3(512), 0, st, p); break;
+        // exchange store path A/B (production GEO form): 58000 the round-5 body (32-bit stores),
+        // 58001 32-bit stores + the tail of the large layers in the reads, 58002 production
+        // (64-bit stores), 58003 64-bit stores + the tail in the reads; 58030 .. 58033 = the
+        // same four with the phase timeline (non-GEO form, as 51030)
+        case 58000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 536870912>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58001: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 536870912 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58002: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58003: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58030: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | 536870912>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58031: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | 536870912 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58032: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288>), dim3(grid), dim3(512), 0, st, p); break;
+        case 58033: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
         // XCD-affine queues (needs count % 8 == 0 and the host's zeroed 8-XCD queue words)
         case 57000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 134217728>), dim3(grid), dim3(512), 0, st, p); break;
         case 56000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 67108864>), dim3(grid), dim3(512), 0, st, p); break;

@@ -5,7 +5,9 @@ buffers), records one launch's per-set phase boundaries (thread 0, 100 MHz clock
 and prints the mean duration of every phase in us, per set kind.
 usage: python3 scripts/diag/trace_phases.py [mode ...]   (51030 production + trace,
        51010 LDS-DMA form + trace, 51014 no global memory + trace, 51012 no arithmetic
-       + trace)
+       + trace; the exchange store path A/B: 58030 32-bit stores, 58031 32-bit stores +
+       the tail of the large layers in the reads, 58032 = production, 58033 64-bit stores
+       + the tail in the reads)
 """
 import ctypes
 import json
