@@ -82,9 +82,11 @@ def erasured_root(shares, axis_index: int, square_size: int, ns_size: int = 29, 
     return nmt_root(out, ns_size, ignore_max)
 
 
-def eds_roots(eds, square_size: int, ns_size: int = 29):
+def eds_roots(eds, square_size: int, ns_size: int = 29, ignore_max: bool = True):
     """(row roots, column roots) of a complete [W][W][S] numpy square."""
     W = eds.shape[0]
-    rows = [erasured_root([eds[r, c].tobytes() for c in range(W)], r, square_size, ns_size) for r in range(W)]
-    cols = [erasured_root([eds[r, c].tobytes() for r in range(W)], c, square_size, ns_size) for c in range(W)]
+    rows = [erasured_root([eds[r, c].tobytes() for c in range(W)], r, square_size, ns_size, ignore_max)
+            for r in range(W)]
+    cols = [erasured_root([eds[r, c].tobytes() for r in range(W)], c, square_size, ns_size, ignore_max)
+            for c in range(W)]
     return rows, cols

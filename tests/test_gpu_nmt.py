@@ -5,12 +5,17 @@ buffered vs plain roots for ODS 32..512 and the uneven 35/67/83/127, with a
 pool reused across sizes.  Here both constructors land on the device NMT, so each
 case is also checked against the host restatement (rsm_nmt_tree_root, through a
 Python tree callback) and, up to k = 128, the Python oracle (oracle/nmt.py).
-Parity vs the nmt library itself is unpinned (not vendored)."""
+Parity vs the nmt library itself is unpinned (not vendored).
+The namespaces here are uniform random bytes: never equal, always told apart by byte
+0, never 0xFF.. inside quadrant 0.  Namespace structure (repeats, compares a late byte
+decides, the parity namespace in quadrant 0, ignore_max_namespace = 0, the status word
+of every tree, each wave-kernel form) is tests/test_gpu_nmt_layouts.py's."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import nmt_layouts as NL
 import oracle
 import rsmt2d_amd as R
 from oracle import nmt
@@ -130,6 +135,12 @@ def test_nmt_roots_squares_dev_batched(lib, k, ns, S, count):
     if not np.array_equal(sqs[-1][0, 0, :ns], sqs[-1][0, 1, :ns]):
         assert bad[0] != 0  # row 0's push order
     assert not bad[k:W].any()  # parity rows: parity namespace everywhere past Q0
+    # every status word of the bad square: a tree fails iff two adjacent quadrant-0 cells decrease
+    assert (bad == NL.decreasing_status(sqs[-1], k, ns)).all()
+    if k <= 16:  # and against the oracle, with the roots of the trees it does not fail
+        want_st, want = NL.expected(sqs[-1], k, ns)
+        assert (bad == want_st).all()
+        assert all(bytes(got[count - 1, t]) == r for t, r in enumerate(want) if r is not None)
 
 
 def test_nmt_push_order_error_device_and_host():

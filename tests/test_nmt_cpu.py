@@ -3,7 +3,10 @@ wrappers push it, nmtwrapper_test.go:94-120) -- the host restatement
 rsm_nmt_tree_root (merkle.cpp) against the Python oracle (oracle/nmt.py), its
 error behaviour, and the Python mirror's buffered-constructor plumbing.
 Parity vs the nmt library itself is unpinned (not vendored; no golden vectors in
-the reference) -- see oracle/nmt.py."""
+the reference) -- see oracle/nmt.py.
+The namespaces here are uniform random bytes; structured ones (repeats, compares a
+late byte decides, 0xFF.. inside quadrant 0, IgnoreMaxNamespace off) are
+tests/test_nmt_layouts_cpu.py's."""
 import hashlib
 
 import numpy as np
