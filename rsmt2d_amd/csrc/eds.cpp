@@ -221,15 +221,7 @@ struct DevSquare {
         if (idx.empty()) return RSM_OK;
         hipError_t r = hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st);
         if (r != hipSuccess) return hip_fail(r, "H2D indices");
-        DecodeSet ds{};
-        ds.base = d_eds;
-        ds.presence = d_pres;
-        ds.indices = d_idx;
-        ds.count = (uint32_t)idx.size();
-        ds.axis = (uint32_t)axis;
-        ds.k = k;
-        ds.S = S;
-        return launch_decode(ctx, ds, st);
+        return launch_decode(ctx, decode_vectors(d_eds, k, S, (uint32_t)axis, d_idx, (uint32_t)idx.size(), d_pres), st);
     }
     // verifyEncoding for many complete vectors at once: re-encode their first
     // half into the scratch square and compare parity halves.  bad[i] = 1 on mismatch.
@@ -238,17 +230,7 @@ struct DevSquare {
         if (idx.empty()) return RSM_OK;
         hipError_t r = hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st);
         if (r != hipSuccess) return hip_fail(r, "H2D indices");
-        CodewordSet cs{};
-        cs.base = d_eds;
-        cs.out_base = d_scratch;
-        cs.indices = d_idx;
-        cs.cw_stride = axis == RSM_AXIS_ROW ? (uint64_t)W * S : S;
-        cs.elem_stride = axis == RSM_AXIS_ROW ? S : (uint64_t)W * S;
-        cs.out_offset = axis == RSM_AXIS_ROW ? (uint64_t)k * S : (uint64_t)k * W * S;
-        cs.per_square = 1;
-        cs.count = (uint32_t)idx.size();
-        cs.k = k;
-        cs.S = S;
+        const CodewordSet cs = indexed_vectors(d_eds, k, S, (uint32_t)axis, d_idx, (uint32_t)idx.size(), d_scratch);
         if (int rc = launch_encode(ctx, cs, st)) return rc;
         if ((r = launch_compare_parity(d_eds, d_scratch, k, S, (uint32_t)axis, d_idx, cs.count, d_flags, st)) != hipSuccess)
             return hip_fail(r, "compare parity");
@@ -547,14 +529,7 @@ int fast_repair_rows_zero_copy(rsm_eds* e, DevSquare& dev, const std::vector<uin
     // halves' sweeps on two lanes at once both measured no faster: DESIGN.md §5.)
     auto sweep = [&](size_t t0, size_t t1) -> int {
         if (t1 <= t0) return RSM_OK;
-        DecodeSet ds{};
-        ds.base = dev.d_eds;
-        ds.presence = dev.d_pres;
-        ds.indices = d_rows + t0;
-        ds.count = (uint32_t)(t1 - t0);
-        ds.axis = RSM_AXIS_ROW;
-        ds.k = k;
-        ds.S = e->S;
+        DecodeSet ds = decode_vectors(dev.d_eds, k, e->S, RSM_AXIS_ROW, d_rows + t0, (uint32_t)(t1 - t0), dev.d_pres);
         ds.in_base = static_cast<const uint8_t*>(hmap);
         ds.mirror = static_cast<uint8_t*>(hmap);
         ds.grid = zc_grid;
@@ -604,18 +579,8 @@ int fast_repair_rows_zero_copy(rsm_eds* e, DevSquare& dev, const std::vector<uin
     *h_mismatch = 0;
     memset(status, 0, (size_t)2 * W * 4);
     (void)hipStreamWaitEvent(sv, halves ? ev_top : ev_bot, 0);  // (one event record on st)
-    CodewordSet cols{};
-    cols.base = dev.d_eds;
+    CodewordSet cols = square_cols(dev.d_eds, k, e->S, 1);
     cols.out_base = dev.d_scratch;
-    cols.square_stride = (uint64_t)W * row;
-    cols.cw_stride = S;
-    cols.elem_stride = row;
-    cols.out_offset = (uint64_t)k * row;
-    cols.per_square = W;
-    cols.count = W;
-    cols.k = k;
-    cols.S = e->S;
-    cols.pass = 1;
     if (int rc = launch_encode(dev.ctx, cols, sv)) return rc;
     if (halves) (void)hipStreamWaitEvent(sv, ev_bot, 0);
     e->stats.sweeps++;

@@ -12,39 +12,6 @@
 
 using namespace rsm;
 
-namespace {
-
-[[maybe_unused]] CodewordSet rows_of(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count, uint32_t grid) {
-    const uint64_t W = 2ull * k;
-    CodewordSet rows{};
-    rows.base = rows.out_base = d_eds;
-    rows.square_stride = W * W * S;
-    rows.cw_stride = W * S;
-    rows.elem_stride = S;
-    rows.out_offset = (uint64_t)k * S;
-    rows.per_square = k;
-    rows.count = k * count;
-    rows.k = k;
-    rows.S = S;
-    rows.pass = 0;
-    rows.grid = grid;
-    return rows;
-}
-
-CodewordSet cols_of(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count, uint32_t grid) {
-    CodewordSet cols = rows_of(d_eds, k, S, count, grid);
-    const uint64_t W = 2ull * k;
-    cols.cw_stride = S;
-    cols.elem_stride = W * S;
-    cols.out_offset = (uint64_t)k * W * S;
-    cols.per_square = (uint32_t)W;
-    cols.count = (uint32_t)W * count;
-    cols.pass = 1;
-    return cols;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rsm_diag_set_bs_mode(int mode, int rev_col, int xcd) {
@@ -115,7 +82,7 @@ int rsm_diag_extend_fused(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_
         return fail(RSM_EINVAL, "rsm_diag_extend_fused: needs k = 128 and k * S a multiple of 2 KiB");
     if (count == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     // delay bits 0-7: squares; bits 8-15 (if non-zero): the Q1 claim margin + 1
     const uint32_t m = (delay >> 8) & 0xFFu;
     const int rc = extend_squares_queue(ctx, static_cast<uint8_t*>(d_eds), k, share_size, count, st, delay & 0xFFu,
@@ -127,7 +94,7 @@ int rsm_diag_extend_fused(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_
 int rsm_diag_queue_check(rsm_ctx* ctx, void* stream) {
     if (!ctx) return fail(RSM_EINVAL, "rsm_diag_queue_check: bad arguments");
     if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return check_queue_reports(ctx, st);
@@ -141,9 +108,10 @@ int rsm_diag_extend_pipeline_dev(rsm_ctx* ctx, void* d_rows_eds, void* d_cols_ed
     if (int rc = validate_chunk_size(share_size)) return rc;
     if (count == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    const CodewordSet rows = rows_of(static_cast<uint8_t*>(d_rows_eds), k, share_size, count, ctx->cus);
-    const CodewordSet cols = cols_of(static_cast<uint8_t*>(d_cols_eds), k, share_size, count, ctx->cus);
+    hipStream_t st = pick(ctx, stream);
+    CodewordSet rows = square_rows(static_cast<uint8_t*>(d_rows_eds), k, share_size, count);
+    CodewordSet cols = square_cols(static_cast<uint8_t*>(d_cols_eds), k, share_size, count);
+    rows.grid = cols.grid = ctx->cus;  // the dual launch reads it: every CU
     const bool dual = field_bits(k) == 8 && d_rows_eds && d_cols_eds && bs128_applicable(rows) && bs128_applicable(cols);
     if (!dual) {
         if (d_rows_eds)

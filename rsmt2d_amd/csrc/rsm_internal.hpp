@@ -153,6 +153,92 @@ struct LaneGuard {
 
 StreamScratch& stream_scratch(rsm_ctx* ctx, hipStream_t st);
 
+// The caller's stream of a C ABI call, NULL meaning the context's own.
+inline hipStream_t pick(rsm_ctx* ctx, void* stream) { return stream ? static_cast<hipStream_t>(stream) : ctx->stream; }
+
+// ---------------------------------------------------------------------------
+// Descriptor builders: the one place where the row and column layout of a
+// [2k][2k][S] square (defined at rsm_kernels.hpp:14-20) is written as code.  Each
+// returns a zeroed descriptor with every layout field set and out_base = base;
+// chunks, grid and wide are set by launch_encode, launch_decode and the queue path.
+// ---------------------------------------------------------------------------
+// `count` row (axis 0) or column (axis 1) codewords, `per_square` of them in a square,
+// the first one at `first`; pass = axis.
+inline CodewordSet axis_set(uint8_t* first, uint32_t k, uint32_t S, uint32_t axis, uint32_t per_square, uint32_t count) {
+    const uint64_t row = 2ull * k * S;
+    CodewordSet cs{};
+    cs.base = cs.out_base = first;
+    cs.cw_stride = axis ? S : row;
+    cs.elem_stride = axis ? row : S;
+    cs.out_offset = k * cs.elem_stride;
+    cs.per_square = per_square;
+    cs.count = count;
+    cs.k = k;
+    cs.S = S;
+    cs.pass = axis;
+    return cs;
+}
+// Rows 0 .. k-1 (Q0 -> Q1) / all 2k columns ([Q0|Q1] -> [Q2|Q3]) of `count` consecutive squares.
+inline CodewordSet square_rows(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count) {
+    CodewordSet cs = axis_set(d_eds, k, S, 0, k, k * count);
+    cs.square_stride = 4ull * k * k * S;
+    return cs;
+}
+inline CodewordSet square_cols(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count) {
+    CodewordSet cs = axis_set(d_eds, k, S, 1, 2 * k, 2 * k * count);
+    cs.square_stride = 4ull * k * k * S;
+    return cs;
+}
+// Rows [row0, row0 + n) / columns [col0, col0 + n) of ONE square.  square_stride stays 0:
+// bs128_applicable() reads it to decide whether the bit-sliced kernel's offsets fit.
+inline CodewordSet slice_rows(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t row0, uint32_t n) {
+    return axis_set(d_eds + 2ull * k * S * row0, k, S, 0, n, n);
+}
+inline CodewordSet slice_cols(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t col0, uint32_t n) {
+    return axis_set(d_eds + (uint64_t)S * col0, k, S, 1, n, n);
+}
+// One stand-alone codeword (the Codec's Encode): k data shares, then k parity shares;
+// launched as a column pass.
+inline CodewordSet single_codeword(uint8_t* base, uint32_t k, uint32_t S) {
+    CodewordSet cs = axis_set(base, k, S, 0, 1, 1);
+    cs.cw_stride = 0;
+    cs.pass = 1;
+    return cs;
+}
+// The two index-list forms take (d_eds, k, S, axis, indices, count, ...), like the rest.
+// Rows or columns indices[0 .. count) of one square, their parity written relative to
+// `out` (Repair's verifyEncoding); launched as a row pass on either axis.
+inline CodewordSet indexed_vectors(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t axis, const uint32_t* indices,
+                                   uint32_t count, uint8_t* out) {
+    CodewordSet cs = axis_set(d_eds, k, S, axis, 1, count);
+    cs.out_base = out;
+    cs.indices = indices;
+    cs.pass = 0;
+    return cs;
+}
+// Rows or columns indices[0 .. count) of one square to reconstruct in place; the
+// zero-copy fields (in_base, mirror, grid) are the caller's to assign.
+inline DecodeSet decode_vectors(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t axis, const uint32_t* indices,
+                                uint32_t count, const uint8_t* presence) {
+    DecodeSet ds{};
+    ds.base = d_eds;
+    ds.presence = presence;
+    ds.indices = indices;
+    ds.count = count;
+    ds.axis = axis;
+    ds.k = k;
+    ds.S = S;
+    return ds;
+}
+// Persistent-grid size of a pass (0 = rows, else columns) of the bit-sliced launches:
+// its cap (rsm_ctx_set_pass_grid) when that is set and below the CU count, else every CU.
+inline uint32_t pass_grid_size(const rsm_ctx* ctx, uint32_t pass) {
+    const uint32_t cap = ctx->pass_grid[pass == 0 ? 0 : 1].load(std::memory_order_relaxed);
+    return cap && cap < ctx->cus ? cap : ctx->cus;
+}
+// CodewordSet::chunks / DecodeSet::chunks of the GF(2^8) launches: 256 bytes per wave.
+inline uint32_t chunks_of(uint32_t S) { return (S + 255) / 256; }
+
 // GF(2^16) tables on the context's device (uploaded once).  Returns RSM_OK or an RSM_E* code.
 int ensure_gf16_tables(rsm_ctx* ctx);
 

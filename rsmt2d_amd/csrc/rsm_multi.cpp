@@ -56,17 +56,7 @@ bool shard_fused_ok(const rsm_ctx* ctx, uint32_t k, uint32_t S, int G) {
 // snd + h * blk: the GPU's rows x GPU h's ck columns, row pitch ck * S)
 int rows_with_side(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t row0, uint32_t nrows, uint8_t* snd,
                    uint64_t blk, uint32_t ck, uint32_t self) {
-    const uint64_t W = 2ull * k;
-    CodewordSet cs{};
-    cs.base = d_eds + row0 * W * S;
-    cs.cw_stride = W * S;
-    cs.elem_stride = S;
-    cs.out_offset = (uint64_t)k * S;
-    cs.per_square = nrows;
-    cs.count = nrows;
-    cs.k = k;
-    cs.S = S;
-    cs.pass = 0;
+    CodewordSet cs = slice_rows(d_eds, k, S, row0, nrows);
     cs.side = snd;
     cs.side_blk = blk;
     cs.side_cols = ck;
@@ -78,17 +68,7 @@ int rows_with_side(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, uint32_
 // received blocks `rcv` (block h at rcv + h * blk: GPU h's rk rows x these columns)
 int cols_with_blocks(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t col0, uint32_t ncols,
                      const uint8_t* rcv, uint64_t blk, uint32_t rk, uint32_t self) {
-    const uint64_t W = 2ull * k;
-    CodewordSet cs{};
-    cs.base = d_eds + col0 * S;
-    cs.cw_stride = S;
-    cs.elem_stride = W * S;
-    cs.out_offset = (uint64_t)k * W * S;
-    cs.per_square = ncols;
-    cs.count = ncols;
-    cs.k = k;
-    cs.S = S;
-    cs.pass = 1;
+    CodewordSet cs = slice_cols(d_eds, k, S, col0, ncols);
     cs.blk = rcv;
     cs.blk_size = blk;
     cs.blk_rows = rk;

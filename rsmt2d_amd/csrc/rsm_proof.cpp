@@ -14,8 +14,6 @@ static_assert(sizeof(rsm_sample) == sizeof(ProofSample) && sizeof(rsm_sample) ==
 
 namespace {
 
-hipStream_t pick(rsm_ctx* ctx, void* stream) { return stream ? static_cast<hipStream_t>(stream) : ctx->stream; }
-
 // The device tree of (width, nmt), or false beyond the root kernels' limits.
 bool proof_tree_for(uint32_t width, const rsm_nmt_params* nmt, DevTree* t) {
     return device_tree_for(nmt ? rsm_nmt_tree_root : nullptr, const_cast<rsm_nmt_params*>(nmt), width, t);

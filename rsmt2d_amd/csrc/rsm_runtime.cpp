@@ -238,9 +238,8 @@ int launch_encode(rsm_ctx* ctx, const CodewordSet& cs0, hipStream_t st) {
         if (cs.wide) {
             e = launch_encode_gf8_wide(cs, st);
         } else {
-            cs.chunks = (cs.S + 255) / 256;
-            const uint32_t cap = ctx->pass_grid[cs.pass == 0 ? 0 : 1].load(std::memory_order_relaxed);
-            cs.grid = (cap > 0 && cap < ctx->cus) ? cap : ctx->cus;
+            cs.chunks = chunks_of(cs.S);
+            cs.grid = pass_grid_size(ctx, cs.pass);
             e = launch_encode_gf8(cs, st);
         }
     } else {
@@ -283,7 +282,7 @@ int launch_decode(rsm_ctx* ctx, const DecodeSet& ds0, hipStream_t st) {
         if (ds.wide) {
             e = launch_decode_gf8_wide(ds, st);
         } else {
-            ds.chunks = (ds.S + 255) / 256;
+            ds.chunks = chunks_of(ds.S);
             e = launch_decode_gf8(ds, st);
         }
     } else {
@@ -323,34 +322,7 @@ int launch_decode(rsm_ctx* ctx, const DecodeSet& ds0, hipStream_t st) {
 // Phase 2 computes Q2 exactly as erasureExtendCol and Q3 by column-encoding Q1,
 // which equals the reference's row-encoding of Q2 by linearity of the 2D code
 // (extendeddatasquare.go:204-207; asserted in tests against the oracle, which
-// runs the reference order).
-static CodewordSet rows_set(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count) {
-    const uint64_t W = 2ull * k;
-    CodewordSet rows{};
-    rows.base = rows.out_base = d_eds;
-    rows.square_stride = W * W * S;
-    rows.cw_stride = W * S;
-    rows.elem_stride = S;
-    rows.out_offset = (uint64_t)k * S;
-    rows.per_square = k;
-    rows.count = k * count;
-    rows.k = k;
-    rows.S = S;
-    rows.pass = 0;
-    return rows;
-}
-
-static CodewordSet cols_set(uint8_t* d_eds, uint32_t k, uint32_t S, uint32_t count) {
-    const uint64_t W = 2ull * k;
-    CodewordSet cols = rows_set(d_eds, k, S, count);
-    cols.cw_stride = S;
-    cols.elem_stride = W * S;
-    cols.out_offset = (uint64_t)k * W * S;
-    cols.per_square = (uint32_t)W;
-    cols.count = (uint32_t)W * count;
-    cols.pass = 1;
-    return cols;
-}
+// runs the reference order).  The two descriptors: square_rows() / square_cols().
 
 int check_queue_reports(rsm_ctx* ctx, hipStream_t st) {
     bool stuck = false;
@@ -397,12 +369,11 @@ int extend_squares_queue(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, u
     if (field_bits(k) != 8 || count == 0) return RSM_EUNSUPPORTED;
     QueuePlan p{};
     // parity from its own base: the symbol offsets span one half (narrow_fits)
-    p.rows = rebased(rows_set(d_eds, k, S, count));
-    p.cols = rebased(cols_set(d_eds, k, S, count));
-    // persistent grid: every CU, or the row-pass cap of rsm_ctx_set_pass_grid
-    const uint32_t cap = ctx->pass_grid[0].load(std::memory_order_relaxed);
-    p.rows.grid = p.cols.grid = cap && cap < ctx->cus ? cap : ctx->cus;
-    p.rows.chunks = p.cols.chunks = (S + 255) / 256;
+    p.rows = rebased(square_rows(d_eds, k, S, count));
+    p.cols = rebased(square_cols(d_eds, k, S, count));
+    // one persistent grid for both passes: the row pass's
+    p.rows.grid = p.cols.grid = pass_grid_size(ctx, 0);
+    p.rows.chunks = p.cols.chunks = chunks_of(S);
     if (!bs128_queue_applicable(p.rows, p.cols)) return RSM_EUNSUPPORTED;
     if (int rc = check_queue_reports(ctx, st)) return rc;
     p.count = count;
@@ -442,8 +413,8 @@ int extend_squares_split(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, u
     // 9 <= k <= 64 (M = 16, 32, 64; round 6): the split form too (encode_gf8_splitm_kernel)
     // for up to split_max squares; larger batches take the byte-table passes
     if (M != 128 && M != 16 && M != 32 && M != 64) return RSM_EUNSUPPORTED;
-    const CodewordSet rows = rows_set(d_eds, k, S, count);
-    CodewordSet c0 = cols_set(d_eds, k, S, count);  // columns 0 .. k-1 (Q0 -> Q2)
+    const CodewordSet rows = square_rows(d_eds, k, S, count);
+    CodewordSet c0 = square_cols(d_eds, k, S, count);  // columns 0 .. k-1 (Q0 -> Q2)
     c0.per_square = k;
     c0.count = k * count;
     CodewordSet c1 = c0;  // columns k .. 2k-1 (Q1 -> Q3)
@@ -452,7 +423,7 @@ int extend_squares_split(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, u
     // one square: ONE launch whose Q1-column workgroups wait on the device for the row
     // tasks -- 3 k ceil(S / 256) workgroups of 8 waves, resident at once when they fit
     // 4 per CU (otherwise the two launches below)
-    const uint64_t wgs = 3ull * k * ((S + 255) / 256);
+    const uint64_t wgs = 3ull * k * chunks_of(S);
     if (M == 128 && count == 1 && wgs <= 4ull * ctx->cus && split_fused_enabled()) {
         if (int rc = check_queue_reports(ctx, st)) return rc;
         StreamScratch& ss = stream_scratch(ctx, st);
@@ -497,33 +468,10 @@ int extend_squares(rsm_ctx* ctx, uint8_t* d_eds, uint32_t k, uint32_t S, uint32_
         const int rc = extend_squares_queue(ctx, d_eds, k, S, count, st);
         if (rc != RSM_EUNSUPPORTED) return rc;
     }
-    if (phases & 1) {
-        CodewordSet rows{};
-        rows.base = d_eds;
-        rows.square_stride = W * W * S;
-        rows.cw_stride = W * S;
-        rows.elem_stride = S;
-        rows.out_offset = (uint64_t)k * S;
-        rows.per_square = k;
-        rows.count = k * count;
-        rows.k = k;
-        rows.S = S;
-        rows.pass = 0;
-        if (int rc = launch_encode(ctx, rows, st)) return rc;
-    }
+    if (phases & 1)
+        if (int rc = launch_encode(ctx, square_rows(d_eds, k, S, count), st)) return rc;
     if (!(phases & 2)) return RSM_OK;
-    CodewordSet cols{};
-    cols.base = d_eds;
-    cols.square_stride = W * W * S;
-    cols.cw_stride = S;
-    cols.elem_stride = W * S;
-    cols.out_offset = (uint64_t)k * W * S;
-    cols.per_square = (uint32_t)W;
-    cols.count = (uint32_t)W * count;
-    cols.k = k;
-    cols.S = S;
-    cols.pass = 1;
-    return launch_encode(ctx, cols, st);
+    return launch_encode(ctx, square_cols(d_eds, k, S, count), st);
 }
 
 int device_roots(rsm_ctx* ctx, const uint8_t* d_eds, uint32_t W, uint32_t S, uint8_t* d_roots, hipStream_t st,
@@ -761,15 +709,7 @@ int rsm_encode(rsm_ctx* ctx, const uint8_t* const* data, uint32_t k, uint32_t sh
             // GF(2^8): the latency form (the split byte-table encoder: one 8-wave
             // workgroup per 256-B chunk); GF(2^16): the single-pass encoder -- straight on
             // the pinned buffer
-            CodewordSet cs{};
-            cs.base = cs.out_base = hd;
-            cs.elem_stride = S;
-            cs.out_offset = (uint64_t)k * S;
-            cs.per_square = 1;
-            cs.count = 1;
-            cs.k = k;
-            cs.S = share_size;
-            cs.pass = 1;
+            const CodewordSet cs = single_codeword(hd, k, share_size);
             if (field_bits(k) == 8) {
                 if ((e = launch_encode_gf8_split(cs, nullptr, L.stream, kSplitWavesOne)) != hipSuccess)
                     return hip_fail(e, "encode kernel launch");
@@ -783,16 +723,7 @@ int rsm_encode(rsm_ctx* ctx, const uint8_t* const* data, uint32_t k, uint32_t sh
     uint8_t* d = static_cast<uint8_t*>(L.dev.ptr);
     if ((e = hipMemcpyAsync(d, h, k * S, hipMemcpyHostToDevice, L.stream)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync H2D");
-    CodewordSet cs{};
-    cs.base = d;
-    cs.elem_stride = S;
-    cs.out_offset = (uint64_t)k * S;
-    cs.per_square = 1;
-    cs.count = 1;
-    cs.k = k;
-    cs.S = share_size;
-    cs.pass = 1;
-    if (int rc = launch_encode(ctx, cs, L.stream)) return rc;
+    if (int rc = launch_encode(ctx, single_codeword(d, k, share_size), L.stream)) return rc;
     if ((e = hipMemcpyAsync(h + k * S, d + k * S, k * S, hipMemcpyDeviceToHost, L.stream)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync D2H");
     if ((e = lane_wait(L.stream)) != hipSuccess) return hip_fail(e, "encode");
@@ -833,18 +764,12 @@ int rsm_decode(rsm_ctx* ctx, uint8_t* const* shares, const uint8_t* present, uin
     }
     uint8_t* hp = h + bytes;
     for (uint32_t i = 0; i < n; ++i) hp[i] = present[i] ? 1 : 0;
+    // a single codeword is row 0 of a 1 x 2k "square"
+    const uint32_t* const row0 = static_cast<const uint32_t*>(ctx->zero_index.ptr);
     if (hd) {
         // the decoder straight on the pinned buffer: it reads the points and the
         // presence bytes over PCIe and writes only the missing shares back
-        DecodeSet ds{};
-        ds.base = hd;
-        ds.presence = hd + bytes;
-        ds.indices = static_cast<const uint32_t*>(ctx->zero_index.ptr);
-        ds.count = 1;
-        ds.axis = 0;
-        ds.k = k;
-        ds.S = share_size;
-        if (int rc = launch_decode(ctx, ds, L.stream)) return rc;
+        if (int rc = launch_decode(ctx, decode_vectors(hd, k, share_size, 0, row0, 1, hd + bytes), L.stream)) return rc;
         if ((e = lane_wait(L.stream)) != hipSuccess) return hip_fail(e, "decode");
         for (uint32_t i = 0; i < n; ++i)
             if (!present[i]) memcpy(shares[i], h + i * S, S);
@@ -856,15 +781,7 @@ int rsm_decode(rsm_ctx* ctx, uint8_t* const* shares, const uint8_t* present, uin
         return hip_fail(e, "hipMemcpyAsync H2D");
     if ((e = hipMemcpyAsync(dpres, hp, n, hipMemcpyHostToDevice, L.stream)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync H2D");
-    DecodeSet ds{};
-    ds.base = d;
-    ds.presence = dpres;
-    ds.indices = static_cast<const uint32_t*>(ctx->zero_index.ptr);
-    ds.count = 1;
-    ds.axis = 0;  // a single codeword is row 0 of a 1 x 2k "square"
-    ds.k = k;
-    ds.S = share_size;
-    if (int rc = launch_decode(ctx, ds, L.stream)) return rc;
+    if (int rc = launch_decode(ctx, decode_vectors(d, k, share_size, 0, row0, 1, dpres), L.stream)) return rc;
     if ((e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, L.stream)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync D2H");
     if ((e = lane_wait(L.stream)) != hipSuccess) return hip_fail(e, "decode");
@@ -967,10 +884,6 @@ int rsm_host_free(rsm_ctx* ctx, void* p) {
     return e == hipSuccess ? RSM_OK : hip_fail(e, "hipHostFree");
 }
 
-static hipStream_t pick(rsm_ctx* ctx, void* stream) {
-    return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-}
-
 int rsm_extend_squares_dev(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_size, uint32_t count,
                            void* stream) {
     if (!ctx || !d_eds || k == 0) return fail(RSM_EINVAL, "rsm_extend_squares_dev: bad arguments");
@@ -998,18 +911,7 @@ int rsm_extend_rows_dev(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_si
     if (int rc = validate_chunk_size(share_size)) return rc;
     if (nrows == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    const uint64_t W = 2ull * k, S = share_size;
-    CodewordSet cs{};
-    cs.base = static_cast<uint8_t*>(d_eds) + row0 * W * S;
-    cs.cw_stride = W * S;
-    cs.elem_stride = S;
-    cs.out_offset = k * S;
-    cs.per_square = nrows;
-    cs.count = nrows;
-    cs.k = k;
-    cs.S = share_size;
-    cs.pass = 0;
-    return launch_encode(ctx, cs, pick(ctx, stream));
+    return launch_encode(ctx, slice_rows(static_cast<uint8_t*>(d_eds), k, share_size, row0, nrows), pick(ctx, stream));
 }
 
 int rsm_extend_rows_blocks_dev(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_size, uint32_t row0,
@@ -1029,16 +931,7 @@ int rsm_extend_rows_blocks_dev(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t s
     // side output; every wave's 32 cells lie in one block when k and the block width are
     // multiples of 32): no copy pass
     if (field_bits(k) == 16 && !gf16_generic(k) && k % 32u == 0 && cb % 32u == 0 && narrow_ok(ctx, k, S, S)) {
-        CodewordSet cs{};
-        cs.base = rows;
-        cs.cw_stride = W * S;
-        cs.elem_stride = S;
-        cs.out_offset = k * S;
-        cs.per_square = nrows;
-        cs.count = nrows;
-        cs.k = k;
-        cs.S = share_size;
-        cs.pass = 0;
+        CodewordSet cs = slice_rows(static_cast<uint8_t*>(d_eds), k, share_size, row0, nrows);
         cs.side = blocks;
         cs.side_blk = blk;
         cs.side_cols = cb;
@@ -1060,18 +953,7 @@ int rsm_extend_cols_dev(rsm_ctx* ctx, void* d_eds, uint32_t k, uint32_t share_si
     if (int rc = validate_chunk_size(share_size)) return rc;
     if (ncols == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    const uint64_t W = 2ull * k, S = share_size;
-    CodewordSet cs{};
-    cs.base = static_cast<uint8_t*>(d_eds) + col0 * S;
-    cs.cw_stride = S;
-    cs.elem_stride = W * S;
-    cs.out_offset = k * W * S;
-    cs.per_square = ncols;
-    cs.count = ncols;
-    cs.k = k;
-    cs.S = share_size;
-    cs.pass = 1;
-    return launch_encode(ctx, cs, pick(ctx, stream));
+    return launch_encode(ctx, slice_cols(static_cast<uint8_t*>(d_eds), k, share_size, col0, ncols), pick(ctx, stream));
 }
 
 int rsm_roots_dev(rsm_ctx* ctx, const void* d_eds, uint32_t width, uint32_t share_size, void* d_roots,
@@ -1130,7 +1012,7 @@ int rsm_encode_batch_dev(rsm_ctx* ctx, const void* d_in, void* d_out, uint32_t k
     if (int rc = validate_chunk_size(share_size)) return rc;
     if (count == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    CodewordSet cs{};
+    CodewordSet cs{};  // caller-supplied strides: the one descriptor written out field by field
     cs.base = static_cast<uint8_t*>(const_cast<void*>(d_in));
     cs.out_base = static_cast<uint8_t*>(d_out);
     cs.cw_stride = cw_stride;
@@ -1152,15 +1034,9 @@ int rsm_decode_vectors_dev(rsm_ctx* ctx, void* d_eds, const uint8_t* d_presence,
     if (int rc = validate_chunk_size(share_size)) return rc;
     if (count == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
-    DecodeSet ds{};
-    ds.base = static_cast<uint8_t*>(d_eds);
-    ds.presence = d_presence;
-    ds.indices = d_indices;
-    ds.count = count;
-    ds.axis = (uint32_t)axis;
-    ds.k = k;
-    ds.S = share_size;
-    return launch_decode(ctx, ds, pick(ctx, stream));
+    return launch_decode(ctx, decode_vectors(static_cast<uint8_t*>(d_eds), k, share_size, (uint32_t)axis, d_indices, count,
+                                             d_presence),
+                         pick(ctx, stream));
 }
 
 }  // extern "C"
@@ -1244,7 +1120,7 @@ int rsm_dev_equal(rsm_ctx* ctx, const void* a, const void* b, uint64_t bytes, vo
     if (int rc = use_device(ctx)) return rc;
     LaneGuard g(ctx);
     if (!g.lane) return g.rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     hipError_t e;
     uint32_t word = 1;
     if ((e = g.lane->aux.ensure(64)) != hipSuccess ||
@@ -1261,7 +1137,7 @@ int rsm_dev_equal(rsm_ctx* ctx, const void* a, const void* b, uint64_t bytes, vo
 int rsm_stream_check(rsm_ctx* ctx, void* stream) {
     if (!ctx) return fail(RSM_EINVAL, "rsm_stream_check: NULL ctx");
     if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    hipStream_t st = pick(ctx, stream);
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return check_queue_reports(ctx, st);

@@ -1,10 +1,13 @@
-// hip_stub.cpp -- TEST INFRASTRUCTURE ONLY (tests/test_tsan_cpu.py): a host-memory
+// hip_stub.cpp -- TEST INFRASTRUCTURE ONLY (tests/test_tsan_cpu.py; with RSM_STUB_ORACLE
+// tests/test_multi_cpu.py and tests/test_abi_cpu.py): a host-memory
 // stand-in for the HIP runtime calls and kernel launchers that the product's host
 // code (rsm_runtime.cpp, eds.cpp) makes, so that code can be built with
 // -fsanitize=thread and hammered from many threads on a machine without a GPU.
-// "Kernels" here only touch the bytes a real launch would read and write (so the
-// sanitizer sees every buffer access); they compute nothing meaningful, and
-// nothing in the product links this file.
+// In the plain build the "kernels" only touch the bytes a real launch would read and
+// write (so the sanitizer sees every buffer access) and compute nothing meaningful.
+// With RSM_STUB_ORACLE the encode, decode, parity-compare and DefaultTree-root launches
+// compute the real results on the host (the C oracle, merkle.cpp), so the descriptors
+// the host code builds are checked by their bytes.  Nothing in the product links this file.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -12,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/rsmt2d_hip.h"
 #include "../../rsmt2d_amd/csrc/gf16.hpp"
 #include "../../rsmt2d_amd/csrc/rsm_kernels.hpp"
 
@@ -94,27 +98,31 @@ static void touch_codewords(const CodewordSet& cs, bool gf16) {
 }
 
 #ifdef RSM_STUB_ORACLE
-// multi_check (tests/test_multi_cpu.py): "kernels" that compute the real parity
-// with the C oracle, so the product's host code above them (CodewordSet
-// construction, the multi-GPU exchange) is checked bit for bit on the CPU.
+// multi_check (tests/test_multi_cpu.py), abi_check (tests/test_abi_cpu.py): "kernels"
+// that compute the real parity, the real missing cells and the real DefaultTree roots
+// with the C oracle and merkle.cpp, so the product's host code above them (CodewordSet
+// and DecodeSet construction, the multi-GPU exchange) is checked bit for bit on the CPU.
 }  // namespace rsm
 extern "C" int leo_encode(unsigned k, size_t S, const uint8_t* const* data, uint8_t* const* parity);
+extern "C" int leo_decode(unsigned k, size_t S, uint8_t* const* shards, const uint8_t* present);
 namespace rsm {
 static hipError_t oracle_codewords(const CodewordSet& cs) {
+    // no fallback to base: launch_encode() rebases before it launches, so this guards the
+    // launchers the host calls itself (launch_encode_gf8_split)
+    if (!cs.out_base) return hipErrorInvalidValue;
     std::vector<const uint8_t*> d(cs.k);
     std::vector<uint8_t*> p(cs.k);
     for (uint32_t q = 0; q < cs.count; ++q) {
         const uint64_t rel = cs.indices ? (uint64_t)cs.indices[q] * cs.cw_stride
                                         : (uint64_t)(q / cs.per_square) * cs.square_stride +
                                               (uint64_t)(q % cs.per_square) * cs.cw_stride;
-        uint8_t* out = cs.out_base ? cs.out_base : cs.base;
         for (uint32_t e = 0; e < cs.k; ++e) {
             d[e] = cs.base + rel + (uint64_t)e * cs.elem_stride;
             // the all-to-all column pass: another GPU's rows from the received block
             if (cs.blk && e / cs.blk_rows != cs.blk_self)
                 d[e] = cs.blk + (uint64_t)(e / cs.blk_rows) * cs.blk_size + (uint64_t)(e % cs.blk_rows) * cs.blk_pitch +
                        (uint64_t)q * cs.S;
-            p[e] = out + rel + cs.out_offset + (uint64_t)e * cs.elem_stride;
+            p[e] = cs.out_base + rel + cs.out_offset + (uint64_t)e * cs.elem_stride;
         }
         if (leo_encode(cs.k, cs.S, d.data(), p.data()) != 0) return hipErrorInvalidValue;
         if (cs.side)  // the all-to-all row pass: cells of other GPUs' column blocks into their send blocks
@@ -131,6 +139,28 @@ static hipError_t oracle_codewords(const CodewordSet& cs) {
 }
 hipError_t launch_encode_gf8(const CodewordSet& cs, hipStream_t) { return oracle_codewords(cs); }
 hipError_t launch_encode_gf16(const CodewordSet& cs, const Gf16Dev&, hipStream_t) { return oracle_codewords(cs); }
+// A decode launch rebuilds the missing cells of its vectors in place (zero-copy forms:
+// the present cells come from in_base, the rebuilt ones go to mirror as well).
+static hipError_t oracle_decode(const DecodeSet& ds) {
+    const uint64_t W = 2ull * ds.k;
+    std::vector<uint8_t*> sh(W);
+    std::vector<uint8_t> pres(W);
+    for (uint32_t i = 0; i < ds.count; ++i) {
+        const uint64_t vec = ds.indices[i];
+        auto cell = [&](uint64_t e) { return (ds.axis == 0 ? vec * W + e : e * W + vec) * ds.S; };
+        for (uint64_t e = 0; e < W; ++e) {
+            sh[e] = ds.base + cell(e);
+            pres[e] = ds.presence[cell(e) / ds.S] != 0;
+            if (pres[e] && ds.in_base) memcpy(sh[e], ds.in_base + cell(e), ds.S);
+        }
+        if (leo_decode(ds.k, ds.S, sh.data(), pres.data()) != 0) return hipErrorInvalidValue;
+        for (uint64_t e = 0; e < W && ds.mirror; ++e)
+            if (!pres[e]) memcpy(ds.mirror + cell(e), sh[e], ds.S);
+    }
+    return hipSuccess;
+}
+hipError_t launch_decode_gf8(const DecodeSet& ds, hipStream_t) { return oracle_decode(ds); }
+hipError_t launch_decode_gf16(const DecodeSet& ds, const Gf16Dev&, hipStream_t) { return oracle_decode(ds); }
 #else
 hipError_t launch_encode_gf8(const CodewordSet& cs, hipStream_t) {
     touch_codewords(cs, false);
@@ -141,7 +171,6 @@ hipError_t launch_encode_gf16(const CodewordSet& cs, const Gf16Dev& g, hipStream
     touch_codewords(cs, true);
     return hipSuccess;
 }
-#endif
 static void touch_decode(const DecodeSet& ds) {
     const uint64_t W = 2ull * ds.k;
     for (uint32_t i = 0; i < ds.count; ++i) {
@@ -162,6 +191,7 @@ hipError_t launch_decode_gf16(const DecodeSet& ds, const Gf16Dev& g, hipStream_t
     touch_decode(ds);
     return hipSuccess;
 }
+#endif
 hipError_t launch_encode_gf8_wide(const CodewordSet& cs, hipStream_t st) { return launch_encode_gf8(cs, st); }
 hipError_t launch_decode_gf8_wide(const DecodeSet& ds, hipStream_t st) { return launch_decode_gf8(ds, st); }
 bool bs128_applicable(const CodewordSet&) { return false; }
@@ -186,6 +216,19 @@ hipError_t launch_roots(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t s
             d_leaf[(s * (uint64_t)W * W + c) * 8] = d_eds[(s * (uint64_t)W * W + c) * S];
         memset(d_roots + (uint64_t)s * 2 * W * 32, 0, (size_t)2 * W * 32);
     }
+#ifdef RSM_STUB_ORACLE
+    // the real roots (merkle.cpp's host tree): tree t is row (axis 0) or column (axis 1)
+    // t % W of square t / 2W
+    std::vector<const uint8_t*> leaves(W);
+    for (uint32_t t = 0; t < squares * 2 * W; ++t) {
+        const uint32_t axis = t / W % 2;
+        const uint8_t* v = d_eds + (uint64_t)(t / (2 * W)) * W * W * S + (uint64_t)(t % W) * (axis ? 1 : W) * S;
+        for (uint32_t p = 0; p < W; ++p) leaves[p] = v + (uint64_t)p * (axis ? W : 1) * S;
+        uint32_t len = 32;
+        if (rsm_default_tree_root(nullptr, (int)axis, t % W, leaves.data(), W, S, d_roots + (uint64_t)t * 32, &len) != 0)
+            return hipErrorInvalidValue;
+    }
+#endif
     return hipSuccess;
 }
 hipError_t launch_leaf_hashes(const uint8_t* d_cells, uint32_t cells, uint32_t S, uint32_t* d_leaf, hipStream_t) {
@@ -222,9 +265,20 @@ hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32
     *mismatch = memcmp(a, b, n) != 0;
     return hipSuccess;
 }
-hipError_t launch_compare_parity(const uint8_t*, const uint8_t*, uint32_t, uint32_t, uint32_t, const uint32_t*,
-                                 uint32_t count, uint32_t* flags, hipStream_t) {
+hipError_t launch_compare_parity(const uint8_t* a, const uint8_t* b, uint32_t k, uint32_t S, uint32_t axis,
+                                 const uint32_t* indices, uint32_t count, uint32_t* flags, hipStream_t) {
     memset(flags, 0, count * 4);
+#ifdef RSM_STUB_ORACLE
+    // flags[q] = 1 iff the parity half (cells k .. 2k-1) of vector indices[q] differs between a and b
+    const uint64_t W = 2ull * k;
+    for (uint32_t q = 0; q < count; ++q)
+        for (uint64_t e = k; e < W; ++e) {
+            const uint64_t cell = axis == 0 ? indices[q] * W + e : e * W + indices[q];
+            if (memcmp(a + cell * S, b + cell * S, S) != 0) flags[q] = 1;
+        }
+#else
+    (void)a, (void)b, (void)k, (void)S, (void)axis, (void)indices;
+#endif
     return hipSuccess;
 }
 
