@@ -401,8 +401,22 @@ int rsm_eds_repair(rsm_eds* eds, const uint8_t* row_roots, const uint8_t* col_ro
                    rsm_tree_root_fn tree_fn, void* user, rsm_byzantine* byz);
 int rsm_eds_byzantine_shares(const rsm_eds* eds, uint8_t* out, uint8_t* present);
 
-/* Diagnostics: counters of the last Repair (fast device path taken or not,
- * device decode sweeps, codewords decoded). */
+/* Diagnostics: counters of the last Repair on this square (reset by every rsm_eds_repair).
+ *   fast_path        1 when the device fast path repaired the square and its device
+ *                    verification accepted it; 0 otherwise (the pre-repair check
+ *                    failed, the square was already complete, or the exact sequential
+ *                    solver produced the result).
+ *   sweeps           batched device decode sweeps launched by the fast path (one per
+ *                    axis pass); 0 when the pre-repair check already failed.
+ *   decoded_vectors  rows and columns decoded by those sweeps.
+ *   fallback_reason  why the fast path handed over to the exact solver:
+ *                      0  it did not (fast path accepted, or never ran)
+ *                      1  stuck: the sweeps stopped with cells still missing
+ *                      2  encoding: the rebuilt square is not a valid 2D codeword
+ *                      3  roots: a row or column root (or an NMT tree status) differs
+ *                         from the committed one
+ *                    The encoding compare is consulted first, so 3 means the encoding
+ *                    was fine. */
 typedef struct {
     int32_t fast_path;
     uint32_t sweeps;

@@ -103,8 +103,14 @@ class NmtParams(ctypes.Structure):
                 ("square_size", ctypes.c_uint32)]
 
 
+#: rsm_repair_stats.fallback_reason: which step sent the last Repair from the device
+#: fast path to the exact sequential solver (include/rsmt2d_hip.h)
+FALLBACK_NONE, FALLBACK_STUCK, FALLBACK_ENCODING, FALLBACK_ROOTS = 0, 1, 2, 3
+
+
 class RepairStats(ctypes.Structure):
-    _fields_ = [("fast_path", ctypes.c_int32), ("sweeps", ctypes.c_uint32),
+    """rsm_repair_stats (include/rsmt2d_hip.h): counters of the last Repair."""
+    _fields_ =[("fast_path", ctypes.c_int32), ("sweeps", ctypes.c_uint32),
                 ("decoded_vectors", ctypes.c_uint32), ("fallback_reason", ctypes.c_uint32)]
 
 

@@ -10,6 +10,7 @@ import oracle
 import rsmt2d_amd as R
 from oracle import crossword
 from conftest import const_share, rand_shares
+from repair_cases import oracle_repair_keep as _oracle_repair_keep
 
 pytestmark = pytest.mark.gpu
 S = 512  # extendeddatacrossword_test.go:17
@@ -210,28 +211,6 @@ def test_random_byzantine_8x8_matches_oracle(lib, rng):
             assert e is R.ErrUnrepairableDataSquare
             got = "unrepairable"
         assert got == want, trial
-
-
-def _oracle_repair_keep(flat, rr, cr):
-    """oracle crossword.repair, returning ("ok" | "unrepairable" | (axis, index, shares),
-    the square's cells afterwards): the reference leaves the cells it solved in place
-    when it gives up (extendeddatacrossword.go:74-122)."""
-    sq = crossword.Square(list(flat))
-    try:
-        crossword.pre_repair_sanity_check(sq, rr, cr)
-        while True:
-            solved, progress = True, False
-            for i in range(sq.w):
-                s1, p1 = crossword.solve_vector(sq, crossword.Row, i, rr, cr)
-                s2, p2 = crossword.solve_vector(sq, crossword.Col, i, cr, rr)
-                solved = solved and s1 and s2
-                progress = progress or p1 or p2
-            if solved:
-                return "ok", sq.flattened()
-            if not progress:
-                return "unrepairable", sq.flattened()
-    except crossword.Byzantine as b:
-        return (b.axis, b.index, b.shares), sq.flattened()
 
 
 def test_err_rand_byzantine_incremental(lib, rng):
