@@ -346,6 +346,48 @@ int rsm_default_tree_prove(const uint8_t* const* leaves, uint32_t n_leaves, uint
 int rsm_nmt_tree_prove(const rsm_nmt_params* params, uint32_t index, const uint8_t* const* leaves, uint32_t n_leaves,
                        uint32_t leaf_size, uint32_t pos, uint8_t* record_out, uint8_t* root_out);
 
+/* ---- proof verification ------------------------------------------------------------ */
+/* The receiving side: does this share, at this position, belong under this committed
+ * row or column root?  One status word per sample; the first condition that applies
+ * wins. */
+#define RSM_PROOF_OK 0        /* the fold equals the committed root */
+#define RSM_PROOF_MALFORMED 1 /* n_nodes or right_mask differs from what (width, pos) dictates */
+#define RSM_PROOF_ORDER 2     /* NMT only: a fold step has right.min < left.max (HashNode's error) */
+#define RSM_PROOF_ROOT 3      /* the fold completed but differs from the root (NMT: all of
+                                 min || max || digest is compared) */
+#define RSM_PROOF_OCCUPIED 4  /* rsm_eds_import_samples only: verified, but the cell is not nil */
+/* Two rules are part of the contract.  The position is bound: the verifier derives the
+ * node count and every operand side from (width, pos) -- level l contributes when
+ * ((pos >> l) ^ 1) < ceil(width / 2^l), its sibling is the right operand when pos >> l
+ * is even -- and only compares the record's header with them, so a valid proof of leaf p
+ * presented as leaf p' does not verify.  No address depends on record or share contents:
+ * the fold runs over the derived count (<= L), whatever the header says, and record
+ * bytes past the derived nodes are never read.
+ * The leaf is built as the trees build it: DefaultTree H(0x00 || share); NMT
+ * ns || ns || H(0x00 || ns || share) with ns = share[:namespace_size] when
+ * index < square_size and pos < square_size, else 0xFF..; ignore_max_namespace is
+ * honoured in the fold as in HashNode.
+ *
+ * Device form: n samples in one launch.  d_shares [n][share_size] (16-byte aligned) and
+ * d_records [n][rsm_proof_record_bytes] (any alignment) as rsm_proofs_dev writes them,
+ * d_roots [count][2][width][32 or 2 * namespace_size + 32] as rsm_roots_squares_dev /
+ * rsm_nmt_roots_squares_dev write them, d_status [n] uint32.  Sample i is checked
+ * against root (square, axis, index) of d_roots.  `samples` is HOST memory, validated
+ * and copied as in rsm_proofs_dev (n <= 2^24).  No tree is built, so the limits are not
+ * the root kernels': 1 <= width <= 65536, namespace_size 1..32, share_size a multiple of
+ * 64 (NMT: >= namespace_size, else RSM_ETREE).  n == 0 or count == 0 launches nothing.
+ * Asynchronous on `stream`. */
+int rsm_proofs_verify_dev(rsm_ctx* ctx, const void* d_shares, const void* d_records, const void* d_roots,
+                          uint32_t width, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt,
+                          const rsm_sample* samples, uint32_t n, void* d_status, void* stream);
+/* Host restatements (merkle.cpp), any n_leaves >= 1, the same semantics and status
+ * words.  The return value is an argument error only (RSM_EINVAL; RSM_ETREE for a share
+ * shorter than the namespace); a proof that fails returns RSM_OK with *status != 0. */
+int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t n_leaves, uint32_t pos,
+                            const uint8_t* record, const uint8_t* root, uint32_t* status);
+int rsm_nmt_tree_verify(const rsm_nmt_params* params, uint32_t index, const uint8_t* share, uint32_t share_size,
+                        uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root, uint32_t* status);
+
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */
 int rsm_eds_compute(rsm_ctx* ctx, const uint8_t* const* data, const uint32_t* lens, uint64_t n,
@@ -387,6 +429,23 @@ int rsm_eds_roots(rsm_eds* eds, int axis, rsm_tree_root_fn tree_fn, void* user, 
  * on the path. */
 int rsm_eds_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
                    uint8_t* records_out, uint8_t* shares_out);
+
+/* Rebuilding a square from sampled shares: verifies n samples (square = 0; shares
+ * [n][share size], records [n][rsm_proof_record_bytes(width, nmt)]) against the
+ * committed roots (row_roots / col_roots / root_len as rsm_eds_repair takes them) and
+ * sets the cells of those that verify.  tree_fn / user as rsm_eds_proofs.  A sample
+ * addresses cell (index, pos) for a row and (pos, index) for a column and is verified
+ * against row_roots[index] / col_roots[index].  The samples are then applied in order:
+ * status 0 on a nil cell sets it (SetCell; the cached node store is dropped); status 0
+ * on a non-nil cell -- an earlier sample of the same batch included -- becomes
+ * RSM_PROOF_OCCUPIED and the cell is left as it is; any other status writes nothing.
+ * Returns RSM_OK however many samples were rejected; status_out (n words, nullable)
+ * and *accepted (nullable: the number of cells set) report them.  With a context the
+ * verification is one upload and one rsm_proofs_verify_dev; without, the host
+ * restatement per sample.  Results never depend on the path. */
+int rsm_eds_import_samples(rsm_eds* eds, const uint8_t* row_roots, const uint8_t* col_roots, uint32_t root_len,
+                           rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
+                           const uint8_t* shares, const uint8_t* records, uint32_t* status_out, uint32_t* accepted);
 
 typedef struct {
     int32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */

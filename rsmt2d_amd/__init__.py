@@ -33,7 +33,8 @@ __all__ = [
     "ErasuredNamespacedMerkleTreeConstructor", "newErasuredNamespacedMerkleTreeConstructor",
     "TreePool", "newTreePool",
     "ErrUnrepairableDataSquare", "ErrUnevenChunks", "RSMError", "DeviceError",
-    "library", "build", "device_context", "Proof", "Sample", "prove_samples_dev",
+    "library", "build", "device_context", "Proof", "Sample", "prove_samples_dev", "verify_samples_dev",
+    "RSM_PROOF_OK", "RSM_PROOF_MALFORMED", "RSM_PROOF_ORDER", "RSM_PROOF_ROOT", "RSM_PROOF_OCCUPIED",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -47,6 +48,8 @@ Axis = int
 # rsmt2d_hip.h return codes
 RSM_OK, RSM_EINVAL, RSM_ESHARESIZE, RSM_ETOOFEW, RSM_ESHAPE, RSM_EDEVICE = 0, -1, -2, -3, -4, -5
 RSM_ENOMEM, RSM_EUNSUPPORTED, RSM_EUNREPAIRABLE, RSM_EBYZANTINE, RSM_ECELL, RSM_ETREE = -6, -7, -8, -9, -10, -11
+# proof verification status words (one per sample; the first condition that applies wins)
+RSM_PROOF_OK, RSM_PROOF_MALFORMED, RSM_PROOF_ORDER, RSM_PROOF_ROOT, RSM_PROOF_OCCUPIED = 0, 1, 2, 3, 4
 
 
 class RSMError(Exception):
@@ -201,6 +204,11 @@ SIGNATURES = {
     "rsm_default_tree_prove": (_I32, [_VP, _U32, _U32, _U32, _VP, _VP]),
     "rsm_nmt_tree_prove": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _U32, _VP, _VP]),
     "rsm_eds_proofs": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP]),
+    "rsm_proofs_verify_dev": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _U32, _VP, _VP]),
+    "rsm_default_tree_verify": (_I32, [_VP, _U32, _U32, _U32, _VP, _VP, ctypes.POINTER(_U32)]),
+    "rsm_nmt_tree_verify": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _U32, _VP, _VP,
+                                   ctypes.POINTER(_U32)]),
+    "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
 }
 
 
@@ -627,6 +635,17 @@ class Proof:
         right = [nd for i, nd in enumerate(self.nodes) if (self.right_mask >> i) & 1]
         return left[::-1] + right
 
+    def record(self) -> bytes:
+        """The proof record of this proof (include/rsmt2d_hip.h): u32 n_nodes | u32
+        right_mask | the nodes | zeros up to 8 + ceil(log2 numLeaves) node lengths --
+        the inverse of ``_parse_records``."""
+        nl = 32 if self.nmt is None else 2 * int(self.nmt.namespace_size) + 32
+        rb = 8 + (self.numLeaves - 1).bit_length() * nl
+        body = len(self.nodes).to_bytes(4, "little") + self.right_mask.to_bytes(4, "little") + b"".join(self.nodes)
+        if len(body) > rb or any(len(nd) != nl for nd in self.nodes):
+            raise RSMError(RSM_EINVAL, "proof nodes do not fit the tree's record")
+        return body + bytes(rb - len(body))
+
     @property
     def root(self) -> bytes:
         import hashlib
@@ -682,6 +701,29 @@ def prove_samples_dev(buf: "DeviceBuffer", width: int, share_size: int, samples:
         for b in (nodes, recs, shs):
             b.free()
     return _parse_records(rec, sh, [s[1:] for s in samples], width, share_size, nmt)
+
+
+def verify_samples_dev(shares: "DeviceBuffer", records: "DeviceBuffer", roots: "DeviceBuffer", width: int,
+                       share_size: int, samples: Sequence[tuple], nmt: Optional[NmtParams] = None, count: int = 1):
+    """Status words (RSM_PROOF_*) of ``(square, axis, index, pos)`` samples whose shares
+    ([n][share_size]) and proof records are device-resident, as rsm_proofs_dev writes
+    them, against ``roots`` ([count][2][width][root bytes], as rsm_roots_squares_dev /
+    rsm_nmt_roots_squares_dev write them): one rsm_proofs_verify_dev launch."""
+    import numpy as np
+    L, ctx, n = library(), shares.ctx, len(samples)
+    out = np.zeros(n, np.uint32)
+    if n == 0:
+        return out
+    st = DeviceBuffer(n * 4)
+    try:
+        arr = (Sample * n)(*[Sample(*s) for s in samples])
+        _check(L.rsm_proofs_verify_dev(ctx, shares.ptr, records.ptr, roots.ptr, width, share_size, count,
+                                       ctypes.byref(nmt) if nmt is not None else None, arr, n, st.ptr, None))
+        _check(L.rsm_sync(ctx))
+        out[:] = st.download(n * 4).view(np.uint32)
+    finally:
+        st.free()
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -828,6 +870,33 @@ class ExtendedDataSquare:
     def ColProof(self, rowIdx: int, colIdx: int) -> "Proof":
         """Share (rowIdx, colIdx) with its proof against ColRoots()[colIdx]."""
         return self.Proofs([(Col, colIdx, rowIdx)])[0]
+
+    def SetCellsVerified(self, rowRoots: Sequence[bytes], colRoots: Sequence[bytes], proofs: Sequence[tuple],
+                         device: bool = True) -> List[int]:
+        """Verifies sampled shares against the committed roots and sets the cells of
+        those that verify (rsm_eds_import_samples).  ``proofs``: ``(axis, index, pos,
+        Proof)`` -- the share of cell (index, pos) of a row, (pos, index) of a column.
+        Returns one RSM_PROOF_* status per sample: 0 = the cell was set, 4 = verified but
+        the cell already had a value, anything else = rejected, nothing written.
+        ``device=False`` keeps a context-free square on the host restatement."""
+        tf = self._tree_fn
+        if not (tf is None or tf is NewDefaultTree or isinstance(tf, ErasuredNamespacedMerkleTreeConstructor)):
+            raise RSMError(RSM_EUNSUPPORTED, "samples are verified for the DefaultTree and the NMT only")
+        L, n, S = library(), len(proofs), self.shareSize
+        if device:
+            _check(L.rsm_eds_set_context(self._h, device_context(self._device)))
+        keep, fn, user = _tree_callback(tf)
+        if any(len(pr.share) != S for (_a, _i, _p, pr) in proofs):
+            raise RSMError(RSM_EINVAL, "a sampled share is not of the square's share size")
+        arr = (Sample * max(n, 1))(*[Sample(0, a, i, p) for (a, i, p, _pr) in proofs])
+        shares = b"".join(pr.share for (_a, _i, _p, pr) in proofs)
+        records = b"".join(pr.record() for (_a, _i, _p, pr) in proofs)
+        status = (ctypes.c_uint32 * max(n, 1))()
+        root_len = len(rowRoots[0]) if rowRoots else 0
+        rr = b"".join(bytes(r) for r in rowRoots)
+        cr = b"".join(bytes(c) for c in colRoots)
+        _check(L.rsm_eds_import_samples(self._h, rr, cr, root_len, fn, user, arr, n, shares, records, status, None))
+        return [int(status[i]) for i in range(n)]
 
     def repair_stats(self) -> RepairStats:
         st = RepairStats()

@@ -21,6 +21,9 @@
 //                     (nmt_leaf29_kernel: the same for 29-byte namespaces, 16-byte loads);
 //   nmt_tree_kernel : one workgroup per tree, levels ping-pong in LDS; each thread
 //                     lays its node message out in its own LDS bytes and hashes it.
+// Also nmt_nodes_kernel (every node kept: the proofs' node store) and
+// nmt_proof_verify_kernel (one lane per sampled share: leaf, fold of its proof through
+// hash_node, compare with the committed root; any width up to 65536).
 // Namespace sizes up to 32 bytes (Celestia: 29), widths up to 1024 (LDS permitting).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -815,7 +818,237 @@ __global__ __launch_bounds__(256) void nmt_nodes_kernel(uint32_t* __restrict__ s
         status[(uint64_t)blockIdx.y * 2 * W + tw0 + threadIdx.x] = (wg_bad >> threadIdx.x) & 1u;
 }
 
+// ---------------------------------------------------------------------------
+// Proof verification (rsm_kernels.hpp "Proof verification"), NMT: one lane per sample,
+// as kernels_sha.hip's proof_verify_kernel.  The lane derives node count and operand
+// sides from (W, pos) and compares the record's header with them (kProofMalformed),
+// hashes its leaf as the leaf kernels above do (ns = the share's first bytes for a
+// quadrant-0 sample, index < k and pos < k, else 0xFF..), folds the derived number of
+// siblings through hash_node (kProofOrder where one returns false) and compares
+// min || max || digest with its root (kProofRoot).  NS = 29: the streaming leaf of
+// nmt_leaf29_kernel and hash_node_w<29>, nodes read as 22 words and a half-word; NS = 0:
+// any namespace size, the word-load leaf and hash_node on the lane's LDS message bytes.
+// Records and roots sit at any alignment (memcpy loads); nothing past a record's derived
+// nodes is read, and no address depends on what a record or a share holds.
+template <typename T>
+__device__ __forceinline__ T ld_any(const uint8_t* p) {
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+
+// the node min || max || digest at p (2 ns + 32 bytes) as zero-padded big-endian words
+template <int NS>
+__device__ __forceinline__ void node_from_bytes(const uint8_t* p, uint32_t ns, Node& n) {
+    if constexpr (NS == 29) {
+        uint32_t B[23];  // the 90 bytes as big-endian words; B[22]: bytes 88, 89
+#pragma unroll
+        for (int i = 0; i < 22; ++i) B[i] = __builtin_bswap32(ld_any<uint32_t>(p + 4 * i));
+        B[22] = __builtin_bswap32((uint32_t)ld_any<uint16_t>(p + 88));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            n.mn[i] = B[i] & head_mask(29 - 4 * i);
+            n.mx[i] = __builtin_amdgcn_alignbit(B[7 + i], B[8 + i], 24) & head_mask(29 - 4 * i);  // from byte 29
+            n.d[i] = __builtin_amdgcn_alignbit(B[14 + i], B[15 + i], 16);                         // from byte 58
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < (int)kNsWords; ++i) n.mn[i] = n.mx[i] = n.d[i] = 0u;
+#pragma unroll
+        for (int i = 0; i < (int)kMaxNs; ++i)
+            if (i < (int)ns) {
+                n.mn[i >> 2] |= (uint32_t)p[i] << (24 - 8 * (i & 3));
+                n.mx[i >> 2] |= (uint32_t)p[ns + i] << (24 - 8 * (i & 3));
+            }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) n.d[i >> 2] |= (uint32_t)p[2 * ns + i] << (24 - 8 * (i & 3));
+    }
+}
+
+// the leaf node of a share (S a multiple of 64; 16-byte aligned), as nmt_leaf29_kernel
+__device__ __forceinline__ void verify_leaf29(const uint8_t* share, uint32_t S, bool q0, Node& out) {
+    const nv4u* p = reinterpret_cast<const nv4u*>(share);
+    const uint32_t chunks = S / 64u, L = 30u + S;
+    uint32_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = kH0[i];
+    uint32_t hi[8];   // words 8..15 of the previous chunk
+    uint32_t nsw[8];  // the namespace words (chunk 0's first eight)
+    for (uint32_t b = 0; b <= chunks; ++b) {
+        uint32_t cw[16];
+        if (b < chunks) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const nv4u v = p[b * 4u + q];
+                cw[4 * q + 0] = __builtin_bswap32(v.x);
+                cw[4 * q + 1] = __builtin_bswap32(v.y);
+                cw[4 * q + 2] = __builtin_bswap32(v.z);
+                cw[4 * q + 3] = __builtin_bswap32(v.w);
+            }
+        } else {
+            cw[0] = 0x80000000u;  // the pad byte after the share
+#pragma unroll
+            for (int i = 1; i < 16; ++i) cw[i] = 0u;
+        }
+        uint32_t w[16];
+        if (b == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) nsw[i] = cw[i];
+#pragma unroll
+            for (int i = 0; i < 7; ++i)
+                w[i] = q0 ? __builtin_amdgcn_alignbit(i == 0 ? 0u : cw[i - 1], cw[i], 8)
+                          : (i == 0 ? 0x00FFFFFFu : 0xFFFFFFFFu);
+            w[7] = (q0 ? (__builtin_amdgcn_alignbit(cw[6], cw[7], 8) & 0xFFFF0000u) : 0xFFFF0000u) | (cw[0] >> 16);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(hi[i], i < 7 ? hi[i + 1] : cw[0], 16);
+        }
+        if (b < chunks) {
+#pragma unroll
+            for (int i = 8; i < 16; ++i) w[i] = __builtin_amdgcn_alignbit(cw[i - 8], cw[i - 7], 16);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) hi[i] = cw[8 + i];
+        } else {
+#pragma unroll
+            for (int i = 8; i < 15; ++i) w[i] = 0u;
+            w[15] = 8u * L;
+        }
+        sha_block(h, w);
+    }
+#pragma unroll
+    for (int i = 0; i < (int)kNsWords; ++i) out.mn[i] = out.mx[i] = (q0 ? nsw[i] : 0xFFFFFFFFu) & head_mask(29 - 4 * i);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out.d[i] = h[i];
+}
+
+// the same for any namespace size (S >= ns, a multiple of 4), as nmt_leaf_kernel
+__device__ __forceinline__ void verify_leaf(const uint8_t* share, uint32_t S, uint32_t ns, bool q0, Node& out) {
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(share);
+    const int nD = (int)(S / 4u);
+    const int off = 1 + (int)ns;  // message bytes before the share
+    const int L = off + (int)S;   // message length
+    const int m0 = off >> 2;      // first word holding share bytes
+    const uint32_t sh = 8u * (uint32_t)(off & 3);
+    const int nb = (L + 8) / 64 + 1;
+    uint32_t d0[kNsWords + 1];
+#pragma unroll
+    for (int i = 0; i <= (int)kNsWords; ++i) d0[i] = be_word(dw, i < nD ? i : 0);
+    uint32_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = kH0[i];
+    uint32_t prev = 0;
+    for (int b = 0; b < nb; ++b) {
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int m = 16 * b + i;
+            const int p = 4 * m;  // byte position of the word
+            uint32_t pre = 0;
+            if (m <= (int)kNsWords) {  // only block 0 reaches here (m <= 8)
+                const uint32_t lo = d0[i <= (int)kNsWords ? i : 0];
+                const uint32_t hi = i >= 1 && i <= (int)kNsWords + 1 ? d0[i >= 1 ? i - 1 : 0] : 0u;
+                pre = q0 ? __builtin_amdgcn_alignbit(m == 0 ? 0u : hi, lo, 8) : (m == 0 ? 0x00FFFFFFu : 0xFFFFFFFFu);
+            }
+            const int j = m - m0;  // share word index of this message word
+            const uint32_t cur = be_word(dw, j < 0 ? 0 : (j < nD ? j : nD - 1));
+            const uint32_t r2 = __builtin_amdgcn_alignbit(j <= 0 ? 0u : prev, cur, sh);
+            prev = cur;
+            const uint32_t mpre = head_mask(off - p);
+            const uint32_t mr2 = head_mask(L - p) & ~mpre;
+            uint32_t x = (pre & mpre) | (r2 & mr2);
+            if (p <= L && L < p + 4) x |= 0x80u << (8 * (3 - (L - p)));
+            if (b == nb - 1 && i == 15) x = 8u * (uint32_t)L;
+            w[i] = x;
+        }
+        sha_block(h, w);
+    }
+#pragma unroll
+    for (int i = 0; i < (int)kNsWords; ++i) out.mn[i] = out.mx[i] = (q0 ? d0[i] : 0xFFFFFFFFu) & head_mask((int)ns - 4 * i);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out.d[i] = h[i];
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __restrict__ shares,
+                                                               const uint8_t* __restrict__ records,
+                                                               const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
+                                                               uint32_t ns, uint32_t k, uint32_t ignore_max,
+                                                               const ProofSample* __restrict__ samples, uint32_t n,
+                                                               uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // NS == 0: the lanes' node messages
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint32_t L = proof_levels(W), NL = 2u * ns + 32u;
+    const uint8_t* rec = records + (uint64_t)t * (8u + L * NL);
+    uint32_t n_nodes = 0, mask = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t j = sm.pos >> l;
+        if ((j ^ 1u) < proof_level_count(W, l)) {
+            if (!(j & 1u)) mask |= 1u << n_nodes;
+            ++n_nodes;
+        }
+    }
+    if (ld_any<uint32_t>(rec) != n_nodes || ld_any<uint32_t>(rec + 4) != mask) {
+        status[t] = kProofMalformed;
+        return;
+    }
+    const bool q0 = sm.index < k && sm.pos < k, ig = ignore_max != 0;
+    uint8_t* mb = reinterpret_cast<uint8_t*>(lds) + (NS == 0 ? threadIdx.x * (64u * node_blocks(ns)) : 0u);
+    Node acc;
+    if constexpr (NS == 29) verify_leaf29(shares + (uint64_t)t * S, S, q0, acc);
+    else verify_leaf(shares + (uint64_t)t * S, S, ns, q0, acc);
+    bool ordered = true;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        Node nd, l, r, o;
+        node_from_bytes<NS>(rec + 8u + i * NL, ns, nd);
+        const bool right = (mask >> i) & 1u;  // the sibling is the right operand
+#pragma unroll
+        for (int q = 0; q < (int)kNsWords; ++q) {
+            l.mn[q] = right ? acc.mn[q] : nd.mn[q], r.mn[q] = right ? nd.mn[q] : acc.mn[q];
+            l.mx[q] = right ? acc.mx[q] : nd.mx[q], r.mx[q] = right ? nd.mx[q] : acc.mx[q];
+            l.d[q] = right ? acc.d[q] : nd.d[q], r.d[q] = right ? nd.d[q] : acc.d[q];
+        }
+        if constexpr (NS == 0) {
+            if (!hash_node(l, r, ns, ig, mb, o)) ordered = false;
+        } else {
+            static_assert(NS == 0 || WNode<NS>::kW == (int)kNsWords, "a WNode laid out as a Node");
+            WNode<NS> x, y, z;
+#pragma unroll
+            for (int q = 0; q < (int)kNsWords; ++q) x.mn[q] = l.mn[q], x.mx[q] = l.mx[q], y.mn[q] = r.mn[q], y.mx[q] = r.mx[q];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) x.d[q] = l.d[q], y.d[q] = r.d[q];
+            if (!hash_node_w<NS>(x, y, ig, z)) ordered = false;
+#pragma unroll
+            for (int q = 0; q < (int)kNsWords; ++q) o.mn[q] = z.mn[q], o.mx[q] = z.mx[q];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) o.d[q] = z.d[q];
+        }
+        acc = o;
+    }
+    Node rt;
+    node_from_bytes<NS>(roots + (((uint64_t)sm.square * 2u + sm.axis) * W + sm.index) * NL, ns, rt);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int q = 0; q < (int)kNsWords; ++q) diff |= (acc.mn[q] ^ rt.mn[q]) | (acc.mx[q] ^ rt.mx[q]) | (acc.d[q] ^ rt.d[q]);
+    status[t] = !ordered ? kProofOrder : (diff ? kProofRoot : kProofOk);
+}
+
 }  // namespace
+
+hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
+                                   uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max, const ProofSample* d_samples,
+                                   uint32_t n, uint32_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + 255) / 256);
+    if (ns == 29 && S % 64 == 0 && S >= 64)
+        hipLaunchKernelGGL(nmt_proof_verify_kernel<29>, grid, dim3(256), 0, st, d_shares, d_records, d_roots, W, S, ns, k,
+                           ignore_max, d_samples, n, d_status);
+    else
+        hipLaunchKernelGGL(nmt_proof_verify_kernel<0>, grid, dim3(256), (size_t)256 * 64u * node_blocks(ns), st, d_shares,
+                           d_records, d_roots, W, S, ns, k, ignore_max, d_samples, n, d_status);
+    return hipGetLastError();
+}
 
 hipError_t launch_nmt_nodes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
                             uint32_t squares, uint32_t* d_store, uint8_t* d_roots, uint32_t* d_status, hipStream_t st) {

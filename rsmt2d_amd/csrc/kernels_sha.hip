@@ -14,6 +14,9 @@
 //                      (S/64 + 1 blocks); the digest of a cell serves both its row
 //                      tree and its column tree.
 //   tree_root_kernel : a few trees per wave (2W trees), levels in place in LDS.
+// Also tree_nodes_kernel (every node kept: the proofs' node store) and
+// proof_verify_kernel (one lane per sampled share: leaf hash, fold of its proof, compare
+// with the committed root).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -352,7 +355,100 @@ __global__ __launch_bounds__(256) void tree_nodes_kernel(uint32_t* __restrict__ 
     }
 }
 
+// Proof verification (rsm_kernels.hpp "Proof verification"), DefaultTree: one lane per
+// sample.  The lane derives its proof's node count and operand sides from (W, pos) --
+// level l contributes when ((pos >> l) ^ 1) < ceil(W / 2^l), its sibling is the right
+// operand when pos >> l is even, proof_gather_kernel's picture -- and only compares the
+// record's header with them (kProofMalformed).  It then streams its share through
+// SHA-256 as leaf_hash_kernel does, folds the derived number of siblings in registers
+// (two compressions each) and compares with its root: no intermediate buffer.  Records
+// sit at any alignment (memcpy loads: gfx950 global loads need none); nothing past the
+// derived nodes is read, and no address depends on what a record or a share holds.
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+__global__ __launch_bounds__(256) void proof_verify_kernel(const uint8_t* __restrict__ shares,
+                                                           const uint8_t* __restrict__ records,
+                                                           const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
+                                                           const ProofSample* __restrict__ samples, uint32_t n,
+                                                           uint32_t* __restrict__ status) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint32_t L = proof_levels(W);
+    const uint8_t* rec = records + (uint64_t)t * (8u + L * 32u);
+    uint32_t n_nodes = 0, mask = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t j = sm.pos >> l;
+        if ((j ^ 1u) < proof_level_count(W, l)) {
+            if (!(j & 1u)) mask |= 1u << n_nodes;
+            ++n_nodes;
+        }
+    }
+    if (ld_u32(rec) != n_nodes || ld_u32(rec + 4) != mask) {
+        status[t] = kProofMalformed;
+        return;
+    }
+    const v4u* p = reinterpret_cast<const v4u*>(shares + (uint64_t)t * S);
+    uint32_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = kH0[i];
+    uint32_t prev = 0;  // the 0x00 leaf prefix
+    for (uint32_t blk = 0; blk < S / 64u; ++blk) {
+        uint32_t w[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4u v = p[blk * 4u + q];
+            const uint32_t b0 = __builtin_bswap32(v.x), b1 = __builtin_bswap32(v.y);
+            const uint32_t b2 = __builtin_bswap32(v.z), b3 = __builtin_bswap32(v.w);
+            w[4 * q + 0] = shift8(prev, b0);
+            w[4 * q + 1] = shift8(b0, b1);
+            w[4 * q + 2] = shift8(b1, b2);
+            w[4 * q + 3] = shift8(b2, b3);
+            prev = b3;
+        }
+        sha_block(h, w);
+    }
+    {
+        uint32_t w[16];
+        w[0] = (prev << 24) | 0x00800000u;
+#pragma unroll
+        for (int i = 1; i < 15; ++i) w[i] = 0;
+        w[15] = (S + 1u) * 8u;
+        sha_block(h, w);
+    }
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        const uint8_t* nd = rec + 8u + i * 32u;
+        const bool right = (mask >> i) & 1u;  // the sibling is the right operand
+        uint32_t a[8], b[8], o[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const uint32_t x = __builtin_bswap32(ld_u32(nd + 4 * q));
+            a[q] = right ? h[q] : x;
+            b[q] = right ? x : h[q];
+        }
+        node_hash(a, b, o);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) h[q] = o[q];
+    }
+    const uint8_t* rt = roots + (((uint64_t)sm.square * 2u + sm.axis) * W + sm.index) * 32u;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) diff |= h[q] ^ __builtin_bswap32(ld_u32(rt + 4 * q));
+    status[t] = diff ? kProofRoot : kProofOk;
+}
+
 }  // namespace
+
+hipError_t launch_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
+                               uint32_t S, const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(proof_verify_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_shares, d_records, d_roots, W, S,
+                       d_samples, n, d_status);
+    return hipGetLastError();
+}
 
 // Trees a workgroup of the node-store builds takes: as many as fill its 256 lanes at
 // level 1 (at most 32: the NMT build keeps one failure bit per tree in a word).

@@ -536,3 +536,109 @@ extern "C" int rsm_nmt_tree_prove(const rsm_nmt_params* p, uint32_t index, const
     if (root_out) memcpy(root_out, lvl.data(), NB);
     return RSM_OK;
 }
+
+// ---- proof verification (include/rsmt2d_hip.h "proof verification") ----
+// Host restatements of the device verifiers (kernels_sha.hip proof_verify_kernel,
+// kernels_nmt.hip nmt_proof_verify_kernel): node count and operand sides are derived
+// from (n_leaves, pos) and only compared with the record's header; the fold then runs
+// over the derived count and reads nothing past those nodes.
+namespace {
+
+// nodes of the proof of leaf `pos` among n leaves; *mask: bit i set where node i is the
+// right operand
+uint32_t proof_shape(uint32_t n, uint32_t pos, uint32_t* mask) {
+    const uint32_t L = proof_levels_of(n);
+    uint32_t n_nodes = 0, m = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint64_t j = pos >> l, cnt = ((uint64_t)n + (1ull << l) - 1) >> l;
+        if ((j ^ 1u) < cnt) {
+            if (!(j & 1u)) m |= 1u << n_nodes;
+            ++n_nodes;
+        }
+    }
+    *mask = m;
+    return n_nodes;
+}
+
+bool header_matches(const uint8_t* rec, uint32_t n_nodes, uint32_t mask) {
+    uint32_t a = 0, b = 0;
+    for (int i = 0; i < 4; ++i) {
+        a |= (uint32_t)rec[i] << (8 * i);
+        b |= (uint32_t)rec[4 + i] << (8 * i);
+    }
+    return a == n_nodes && b == mask;
+}
+
+}  // namespace
+
+extern "C" int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t n_leaves, uint32_t pos,
+                                       const uint8_t* record, const uint8_t* root, uint32_t* status) {
+    if ((!share && share_size) || !record || !root || !status || n_leaves == 0 || pos >= n_leaves) return RSM_EINVAL;
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
+    if (!header_matches(record, n_nodes, mask)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    Digest acc;
+    {
+        Sha256 s;
+        const uint8_t pre = 0x00;
+        s.update(&pre, 1);
+        s.update(share, share_size);
+        s.final(acc.b);
+    }
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        Digest nd;
+        memcpy(nd.b, record + 8 + (size_t)i * 32, 32);
+        acc = (mask >> i) & 1u ? node_hash(acc, nd) : node_hash(nd, acc);
+    }
+    *status = memcmp(acc.b, root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_tree_verify(const rsm_nmt_params* p, uint32_t index, const uint8_t* share, uint32_t share_size,
+                                   uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root,
+                                   uint32_t* status) {
+    if (!p || !share || !record || !root || !status || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
+        pos >= n_leaves)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    if (share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
+    if (!header_matches(record, n_nodes, mask)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    std::vector<uint8_t> acc(NB), pair(2 * (size_t)NB), ns(nsz, 0xFF);
+    if (index < k && pos < k) memcpy(ns.data(), share, nsz);  // quadrant 0
+    memcpy(acc.data(), ns.data(), nsz);
+    memcpy(acc.data() + nsz, ns.data(), nsz);
+    {
+        Sha256 s;
+        const uint8_t pre = 0x00;
+        s.update(&pre, 1);
+        s.update(ns.data(), nsz);
+        s.update(share, share_size);
+        s.final(acc.data() + 2 * nsz);
+    }
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        const uint8_t* nd = record + 8 + (size_t)i * NB;
+        const bool right = (mask >> i) & 1u;
+        memcpy(pair.data(), right ? acc.data() : nd, NB);
+        memcpy(pair.data() + NB, right ? nd : acc.data(), NB);
+        if (!nmt_pair(pair.data(), pair.data() + NB, nsz, ig, acc.data())) {
+            *status = RSM_PROOF_ORDER;
+            return RSM_OK;
+        }
+        Sha256 s;
+        const uint8_t pre = 0x01;
+        s.update(&pre, 1);
+        s.update(pair.data(), 2 * (size_t)NB);
+        s.final(acc.data() + 2 * nsz);
+    }
+    *status = memcmp(acc.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}

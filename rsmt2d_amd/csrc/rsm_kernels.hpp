@@ -214,6 +214,20 @@ hipError_t launch_proof_gather(const uint32_t* d_store, uint32_t W, uint32_t squ
                                const ProofSample* d_samples, uint32_t n, uint8_t* d_records, hipStream_t st);
 hipError_t launch_share_gather(const uint8_t* d_eds, uint32_t W, uint32_t S, const ProofSample* d_samples, uint32_t n,
                                uint8_t* d_shares, hipStream_t st);
+// Proof verification (DESIGN.md §4 "Verification"; the DefaultTree kernel in
+// kernels_sha.hip, the NMT kernels in kernels_nmt.hip): one lane per sample hashes its
+// share (d_shares: [n][S], 16-byte aligned), folds the siblings of its record
+// (d_records: [n][8 + L * node_len], any alignment) and compares with its root
+// (d_roots: [squares][2][W][node_len]); d_status[n] receives a kProof* word.  The node
+// count and operand sides come from (W, pos) alone: the record's header is only
+// compared with them, and no address depends on record or share contents.  Any
+// 1 <= W <= 65536; every sample must be in range (the host validates them).
+constexpr uint32_t kProofOk = 0, kProofMalformed = 1, kProofOrder = 2, kProofRoot = 3;
+hipError_t launch_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
+                               uint32_t S, const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st);
+hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
+                                   uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max, const ProofSample* d_samples,
+                                   uint32_t n, uint32_t* d_status, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

@@ -1,7 +1,9 @@
 // rsm_proof.cpp -- share inclusion proofs: the C ABI over the node-store builds
 // (kernels_sha.hip, kernels_nmt.hip) and the gather kernels (kernels_proof.hip), and
 // rsm_eds_proofs of the ExtendedDataSquare object (device path with a cached node
-// store; host restatements of merkle.cpp otherwise).  Format: include/rsmt2d_hip.h.
+// store; host restatements of merkle.cpp otherwise); the receiving side:
+// rsm_proofs_verify_dev over the verify kernels (kernels_sha.hip, kernels_nmt.hip) and
+// rsm_eds_import_samples (verify, then SetCell).  Format: include/rsmt2d_hip.h.
 #include "eds_internal.hpp"
 
 #include <algorithm>
@@ -11,6 +13,10 @@
 using namespace rsm;
 
 static_assert(sizeof(rsm_sample) == sizeof(ProofSample) && sizeof(rsm_sample) == 16, "rsm_sample is the kernels' sample");
+
+static_assert(kProofOk == RSM_PROOF_OK && kProofMalformed == RSM_PROOF_MALFORMED && kProofOrder == RSM_PROOF_ORDER &&
+                  kProofRoot == RSM_PROOF_ROOT,
+              "the kernels' status words are the C ABI's");
 
 namespace {
 
@@ -34,6 +40,31 @@ uint32_t first_bad_sample(const rsm_sample* s, uint32_t n, uint32_t count, uint3
 int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
     return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", who, i, s[i].square,
                 s[i].axis, s[i].index, s[i].pos);
+}
+
+// Uploads n samples through the stream's staging buffers (ss.mu held): *ds is the
+// device copy, valid for kernels enqueued on `st` before the next call on it.
+int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
+    hipError_t e;
+    const size_t bytes = (size_t)n * sizeof(rsm_sample);
+    // the staging buffer is free once the previous call's upload has left it; the
+    // device copy is read by that call's kernels, ordered before this upload on `st`
+    if (ss.samp_ev && (e = hipEventSynchronize(ss.samp_ev)) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+    if (!ss.samp_ev && (e = hipEventCreateWithFlags(&ss.samp_ev, hipEventDisableTiming)) != hipSuccess) {
+        ss.samp_ev = nullptr;
+        return hip_fail(e, "hipEventCreate");
+    }
+    if (bytes > ss.samp_dev.cap) {
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+        if ((e = ss.samp_dev.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (samples)");
+    }
+    if ((e = ss.samp_host.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc (samples)");
+    memcpy(ss.samp_host.ptr, samples, bytes);
+    if ((e = hipMemcpyAsync(ss.samp_dev.ptr, ss.samp_host.ptr, bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return hip_fail(e, "H2D samples");
+    if ((e = hipEventRecord(ss.samp_ev, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
+    *ds = static_cast<const ProofSample*>(ss.samp_dev.ptr);
+    return RSM_OK;
 }
 
 }  // namespace
@@ -103,30 +134,122 @@ int rsm_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_
     StreamScratch& ss = stream_scratch(ctx, st);
     std::lock_guard<std::mutex> lk(ss.mu);
     hipError_t e;
-    const size_t bytes = (size_t)n * sizeof(rsm_sample);
-    // the staging buffer is free once the previous call's upload has left it; the
-    // device copy is read by that call's kernels, ordered before this upload on `st`
-    if (ss.samp_ev && (e = hipEventSynchronize(ss.samp_ev)) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
-    if (!ss.samp_ev && (e = hipEventCreateWithFlags(&ss.samp_ev, hipEventDisableTiming)) != hipSuccess) {
-        ss.samp_ev = nullptr;
-        return hip_fail(e, "hipEventCreate");
-    }
-    if (bytes > ss.samp_dev.cap) {
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-        if ((e = ss.samp_dev.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (samples)");
-    }
-    if ((e = ss.samp_host.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc (samples)");
-    memcpy(ss.samp_host.ptr, samples, bytes);
-    if ((e = hipMemcpyAsync(ss.samp_dev.ptr, ss.samp_host.ptr, bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
-        return hip_fail(e, "H2D samples");
-    if ((e = hipEventRecord(ss.samp_ev, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    const auto* ds = static_cast<const ProofSample*>(ss.samp_dev.ptr);
+    const ProofSample* ds = nullptr;
+    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
     if ((e = launch_proof_gather(static_cast<const uint32_t*>(d_nodes), width, count, t.nmt ? t.p.namespace_size : 0u,
                                  ds, n, static_cast<uint8_t*>(d_records), st)) != hipSuccess)
         return hip_fail(e, "proof gather kernel launch");
     if (d_shares && (e = launch_share_gather(static_cast<const uint8_t*>(d_eds), width, share_size, ds, n,
                                              static_cast<uint8_t*>(d_shares), st)) != hipSuccess)
         return hip_fail(e, "share gather kernel launch");
+    return RSM_OK;
+}
+
+int rsm_proofs_verify_dev(rsm_ctx* ctx, const void* d_shares, const void* d_records, const void* d_roots,
+                          uint32_t width, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt,
+                          const rsm_sample* samples, uint32_t n, void* d_status, void* stream) {
+    if (!ctx || width == 0 || width > 65536u || (n && count && (!samples || !d_shares || !d_records || !d_roots || !d_status)))
+        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: bad arguments");
+    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
+        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: namespace size %u (1..32) or square size 0", nmt->namespace_size);
+    if (reinterpret_cast<uintptr_t>(d_shares) & 15u)
+        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: d_shares must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_status) & 3u)
+        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: d_status must be 4-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_verify_dev: at most %u samples per call", 1u << 24);
+    if (n == 0 || count == 0) return RSM_OK;
+    const uint32_t bad = first_bad_sample(samples, n, count, width);
+    if (bad < n) return bad_sample("rsm_proofs_verify_dev", samples, bad);
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const ProofSample* ds = nullptr;
+    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
+    const auto* sh = static_cast<const uint8_t*>(d_shares);
+    const auto* rec = static_cast<const uint8_t*>(d_records);
+    const auto* roots = static_cast<const uint8_t*>(d_roots);
+    const hipError_t e =
+        nmt ? launch_nmt_proof_verify(sh, rec, roots, width, share_size, nmt->namespace_size, nmt->square_size,
+                                      nmt->ignore_max_namespace, ds, n, static_cast<uint32_t*>(d_status), st)
+            : launch_proof_verify(sh, rec, roots, width, share_size, ds, n, static_cast<uint32_t*>(d_status), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "proof verify kernel launch");
+}
+
+int rsm_eds_import_samples(rsm_eds* e, const uint8_t* row_roots, const uint8_t* col_roots, uint32_t root_len,
+                           rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
+                           const uint8_t* shares, const uint8_t* records, uint32_t* status_out, uint32_t* accepted) {
+    if (!e || !row_roots || !col_roots || (n && (!samples || !shares || !records)))
+        return fail(RSM_EINVAL, "rsm_eds_import_samples: bad arguments");
+    const rsm_nmt_params* nmt = nullptr;
+    if (tree_fn == rsm_nmt_tree_root && user) nmt = static_cast<const rsm_nmt_params*>(user);
+    else if (tree_fn != nullptr && tree_fn != rsm_default_tree_root)
+        return fail(RSM_EUNSUPPORTED, "rsm_eds_import_samples: samples are verified for the DefaultTree and the NMT only");
+    const uint32_t W = e->width, S = e->S;
+    if (nmt && (nmt->namespace_size == 0 || nmt->square_size == 0))
+        return fail(RSM_EINVAL, "rsm_eds_import_samples: namespace size or square size 0");
+    const uint32_t NL = nmt ? 2 * nmt->namespace_size + 32 : 32, RB = 8 + proof_levels(W) * NL;
+    if (root_len != NL) return fail(RSM_EINVAL, "rsm_eds_import_samples: roots of %u bytes, the tree's have %u", root_len, NL);
+    if (nmt && S < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    const uint32_t bad = first_bad_sample(samples, n, 1, W);
+    if (bad < n) return bad_sample("rsm_eds_import_samples", samples, bad);
+    if (accepted) *accepted = 0;
+    if (n == 0) return RSM_OK;
+    std::vector<uint32_t> status(n);
+    if (e->ctx && W <= 65536u && n <= (1u << 24) && (!nmt || nmt->namespace_size <= 32)) {
+        rsm_ctx* ctx = e->ctx;
+        std::lock_guard<std::mutex> lk(ctx->eds_mu);
+        if (int rc = use_device(ctx)) return rc;
+        hipStream_t st = ctx->stream;
+        hipError_t r;
+        // one upload: shares | row roots | column roots | records
+        const size_t o_roots = (size_t)n * S, o_rec = o_roots + (size_t)2 * W * NL, total = o_rec + (size_t)n * RB;
+        std::vector<uint8_t> pack(total);
+        memcpy(pack.data(), shares, (size_t)n * S);
+        memcpy(pack.data() + o_roots, row_roots, (size_t)W * NL);
+        memcpy(pack.data() + o_roots + (size_t)W * NL, col_roots, (size_t)W * NL);
+        memcpy(pack.data() + o_rec, records, (size_t)n * RB);
+        DevBuf& in = ctx->eds.scratch;
+        DevBuf& sb = ctx->eds.status;
+        if ((r = in.ensure(total)) != hipSuccess || (r = sb.ensure((size_t)n * 4)) != hipSuccess)
+            return hip_fail(r, "hipMalloc (samples to verify)");
+        auto* d = static_cast<uint8_t*>(in.ptr);
+        if ((r = hipMemcpyAsync(d, pack.data(), total, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return hip_fail(r, "H2D samples to verify");
+        if (int rc = rsm_proofs_verify_dev(ctx, d, d + o_rec, d + o_roots, W, S, 1, nmt, samples, n, sb.ptr, st)) return rc;
+        if ((r = hipMemcpyAsync(status.data(), sb.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(r, "D2H sample statuses");
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(r, "verify stream");
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            const rsm_sample& s = samples[i];
+            const uint8_t* root = (s.axis == RSM_AXIS_ROW ? row_roots : col_roots) + (size_t)s.index * NL;
+            const uint8_t* sh = shares + (size_t)i * S;
+            const uint8_t* rec = records + (size_t)i * RB;
+            const int rc = nmt ? rsm_nmt_tree_verify(nmt, s.index, sh, S, W, s.pos, rec, root, &status[i])
+                               : rsm_default_tree_verify(sh, S, W, s.pos, rec, root, &status[i]);
+            if (rc) return fail(rc, "rsm_eds_import_samples: bad tree parameters");
+        }
+    }
+    uint32_t set = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const rsm_sample& s = samples[i];
+        const uint32_t r = e->rr((int)s.axis, s.index, s.pos), c = e->cc((int)s.axis, s.index, s.pos);
+        if (status[i] == RSM_PROOF_OK) {
+            if (e->has(r, c)) {
+                status[i] = RSM_PROOF_OCCUPIED;
+            } else {
+                e->proofs.drop();  // as SetCell: the cached tree nodes no longer match
+                memcpy(e->cell(r, c), shares + (size_t)i * S, S);
+                e->present[(size_t)r * W + c] = 1;
+                ++set;
+            }
+        }
+        if (status_out) status_out[i] = status[i];
+    }
+    if (accepted) *accepted = set;
     return RSM_OK;
 }
 

@@ -1,0 +1,329 @@
+"""GPU: proof verification on the device -- rsm_proofs_verify_dev (kernels_sha.hip
+proof_verify_kernel, kernels_nmt.hip nmt_proof_verify_kernel) and the device path of
+rsm_eds_import_samples.  Valid proofs are built by levels in Python
+(tests/proof_status.py), every hostile variant of them is derived there, and the
+device's status vector must equal expected_status element for element."""
+import ctypes
+from collections import defaultdict
+
+import numpy as np
+import pytest
+
+import rsmt2d_amd as R
+from oracle import crossword
+import proof_status as P
+import proof_verify as V
+from test_gpu_guard_bands import Guarded
+
+pytestmark = pytest.mark.gpu
+
+TREES = [("default", 0, 1)] + [("nmt", ns, ig) for ns in (8, 29, 32) for ig in (0, 1)]
+
+
+def nmt_params(tree, ns, ig, k):
+    return R.NmtParams(ns, ig, k) if tree == "nmt" else None
+
+
+def place(items, base):
+    """Samples and the roots table for a device call.  base: [count][2][W][node_len],
+    the committed roots.  An item whose root is not the committed one of its (square,
+    axis, index) gets a slot of its own in extra squares appended to the table: the
+    verifier uses square and axis for the root lookup only."""
+    count, _, W, nl = base.shape
+    committed = {}
+    extra, nxt, samples = {}, defaultdict(int), []
+    for it in items:
+        q, a, i, pos = it.sample
+        if (q, a, i) not in committed:
+            committed[(q, a, i)] = base[q, a, i].tobytes()
+        if committed[(q, a, i)] == it.root:
+            samples.append(it.sample)
+            continue
+        key = (i, it.root)
+        if key not in extra:
+            extra[key] = (count + nxt[i] // 2, nxt[i] % 2)
+            nxt[i] += 1
+        samples.append(extra[key] + (i, pos))
+    total = count + (max(nxt.values(), default=0) + 1) // 2
+    roots = np.zeros((total, 2, W, nl), np.uint8)
+    roots[:count] = base
+    for (i, root), (sq, ax) in extra.items():
+        roots[sq, ax, i] = np.frombuffer(root, np.uint8)
+    return samples, roots
+
+
+def device_statuses(items, W, S, p, base):
+    samples, roots = place(items, base)
+    n = len(items)
+    bufs = [R.DeviceBuffer(max(n * S, 16)), R.DeviceBuffer(max(sum(len(it.record) for it in items), 16)),
+            R.DeviceBuffer(roots.nbytes)]
+    try:
+        bufs[0].upload(np.frombuffer(b"".join(it.share for it in items), np.uint8))
+        bufs[1].upload(np.frombuffer(b"".join(it.record for it in items), np.uint8))
+        bufs[2].upload(roots.reshape(-1))
+        return list(R.verify_samples_dev(bufs[0], bufs[1], bufs[2], W, S, samples, nmt=p, count=roots.shape[0]))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def committed_roots(sq):
+    return np.array([[[np.frombuffer(sq.root(q, a, i), np.uint8) for i in range(sq.W)] for a in (0, 1)]
+                     for q in range(sq.count)])
+
+
+def squares_for(W, S, tree, ns, ig, seed, count=3):
+    k = max(W // 2, 1)
+    p = nmt_params(tree, ns, ig, k)
+    batch = np.stack([V.sorted_q0_square(k, S, max(ns, 8), seed + q)[:W, :W] for q in range(count)])
+    assert ns == 0 or batch[:, :k, :k, :ns].any(axis=-1).all()  # non-zero quadrant-0 namespaces
+    return p, P.Squares(batch, p)
+
+
+def check_against_oracle(W, S, tree, ns, ig, seed, samples_of):
+    p, sq = squares_for(W, S, tree, ns, ig, seed)
+    samples = samples_of(W, sq.count)
+    assert {s[0] for s in samples} == set(range(sq.count))
+    items = sq.items(samples)
+    if len(items) % 256 == 0:
+        items.append(items[0])
+    want = P.expect(items, W, p)
+    got = device_statuses(items, W, S, p, committed_roots(sq))
+    bad = [(it.label, it.sample, g, w) for it, g, w in zip(items, got, want) if g != w]
+    assert not bad, (len(bad), bad[:8])
+    # n = 1: the valid proof, and a hostile one
+    for it, w in ((items[0], want[0]), (items[1], want[1])):
+        assert device_statuses([it], W, S, p, committed_roots(sq)) == [w]
+    return want
+
+
+def all_samples(W, count):
+    return [(q, a, i, pos) for q in range(count) for a in (0, 1) for i in range(W) for pos in range(W)]
+
+
+@pytest.mark.parametrize("tree,ns,ig", TREES)
+def test_device_against_oracle_small_widths(lib, tree, ns, ig):
+    """Widths 1 (no nodes), 2 (one level), 6 and 10 (carried-up nodes), 16 (a power of
+    two): all 2 W^2 samples of each of three squares, every mutation."""
+    want = []
+    for W in (1, 2, 6, 10, 16):
+        want += check_against_oracle(W, 64, tree, ns, ig, 100 * W + ns, all_samples)
+    P.assert_covers(want, nmt_params(tree, ns, ig, 1))
+
+
+@pytest.mark.parametrize("tree,ns,ig", TREES)
+def test_device_against_oracle_width_64(lib, tree, ns, ig):
+    want = check_against_oracle(64, 64, tree, ns, ig, 6400 + ns, lambda W, count: P.picked_samples(W, 64 + ns, count, 1000))
+    P.assert_covers(want, nmt_params(tree, ns, ig, 1))
+
+
+@pytest.mark.parametrize("tree,ns,ig,W,S", [("default", 0, 1, 10, 128), ("nmt", 29, 1, 10, 128), ("nmt", 8, 0, 6, 128),
+                                            ("default", 0, 1, 6, 512), ("nmt", 29, 1, 6, 512), ("nmt", 32, 1, 6, 512)])
+def test_device_against_oracle_wider_shares(lib, tree, ns, ig, W, S):
+    want = check_against_oracle(W, S, tree, ns, ig, S + W + ns, all_samples)
+    P.assert_covers(want, nmt_params(tree, ns, ig, 1))
+
+
+def dev_roots(lib, ctx, d, W, S, count, p):
+    nl = P.node_len(p)
+    roots, status = R.DeviceBuffer(count * 2 * W * nl), R.DeviceBuffer(count * 2 * W * 4)
+    if p is None:
+        R._check(lib.rsm_roots_squares_dev(ctx, d.ptr, W, S, count, roots.ptr, None))
+    else:
+        R._check(lib.rsm_nmt_roots_squares_dev(ctx, d.ptr, W, S, count, ctypes.byref(p), roots.ptr, status.ptr, None))
+    R._check(lib.rsm_sync(ctx))
+    assert p is None or not status.download().any()
+    status.free()
+    return roots
+
+
+@pytest.mark.parametrize("tree,W,S,count", [("default", 24, 64, 2), ("nmt", 24, 64, 2), ("default", 256, 512, 1),
+                                            ("nmt", 256, 512, 1)])
+def test_round_trip_on_device(lib, tree, W, S, count):
+    """rsm_proof_nodes_dev -> rsm_proofs_dev -> rsm_proofs_verify_dev with the roots of
+    the root kernels: records and shares never leave the device."""
+    k, ns = W // 2, 29
+    p = nmt_params(tree, ns, 1, k)
+    pp = ctypes.byref(p) if p is not None else None
+    batch = np.stack([V.sorted_q0_square(k, S, ns, 900 + W + q) for q in range(count)])
+    samples = all_samples(W, count) if W <= 24 else P.picked_samples(W, W, count, 700)
+    n = len(samples)
+    ctx = R.device_context(0)
+    rb = int(lib.rsm_proof_record_bytes(W, pp))
+    d, nodes = R.DeviceBuffer(batch.nbytes), R.DeviceBuffer(int(lib.rsm_proof_nodes_bytes(W, pp, count)))
+    recs, shs = R.DeviceBuffer(n * rb), R.DeviceBuffer(n * S)
+    roots = None
+    try:
+        d.upload(batch.reshape(-1))
+        arr = (R.Sample * n)(*[R.Sample(*s) for s in samples])
+        R._check(lib.rsm_proof_nodes_dev(ctx, d.ptr, W, S, count, pp, nodes.ptr, None, None, None))
+        R._check(lib.rsm_proofs_dev(ctx, nodes.ptr, d.ptr, W, S, count, pp, arr, n, recs.ptr, shs.ptr, None))
+        roots = dev_roots(lib, ctx, d, W, S, count, p)
+        st = R.verify_samples_dev(shs, recs, roots, W, S, samples, nmt=p, count=count)
+        assert not st.any(), np.nonzero(st)[0][:8]
+        victim = n // 3
+        byte = shs.download(1, victim * S + S - 1)
+        shs.upload(byte ^ 0x10, victim * S + S - 1)
+        st = R.verify_samples_dev(shs, recs, roots, W, S, samples, nmt=p, count=count)
+        assert st[victim] == P.ROOT and np.count_nonzero(st) == 1
+    finally:
+        for b in (d, nodes, recs, shs, roots):
+            if b is not None:
+                b.free()
+
+
+def prove_host(lib, p, index, leaves, pos):
+    keep, ptrs, _ = R._bufs(leaves)
+    nl = P.node_len(p)
+    rec = ctypes.create_string_buffer(V.record_bytes(len(leaves), nl))
+    root = ctypes.create_string_buffer(nl)
+    if p is None:
+        rc = lib.rsm_default_tree_prove(ptrs, len(leaves), len(leaves[0]), pos, rec, root)
+    else:
+        rc = lib.rsm_nmt_tree_prove(ctypes.byref(p), index, ptrs, len(leaves), len(leaves[0]), pos, rec, root)
+    assert rc == 0
+    return rec.raw, root.raw
+
+
+@pytest.mark.parametrize("tree", ["default", "nmt"])
+def test_widths_beyond_the_root_kernels(lib, tree):
+    """W = 4098 (13 levels, carried-up nodes at the top): the verifier builds no tree, so
+    the root kernels' width limits do not apply.  One row's records from the host
+    restatements, 64 samples, every mutation (the root flips for eight of them: each
+    needs a root slot of 2 W node lengths)."""
+    W, S, ns, index = 4098, 64, 29, 5
+    k = W // 2
+    p = nmt_params(tree, ns, 1, k)
+    nl = P.node_len(p)
+    rng = np.random.default_rng(4098)
+    rows = []
+    for _ in range(2):
+        sh = [rng.integers(0, 256, S, dtype=np.uint8).tobytes() for _ in range(W)]
+        rows.append(sorted(sh[:k], key=lambda s: s[:ns]) + sh[k:])
+    _, other_root = prove_host(lib, p, index, rows[1], 0)
+    positions = sorted({0, 1, k - 1, k, 4095, 4096, 4097} | {int(x) for x in rng.integers(0, W, 57)})[:64]
+    items, root = [], None
+    for n, pos in enumerate(positions):
+        rec, root = prove_host(lib, p, index, rows[0], pos)
+        for it in P.mutations(rows[0][pos], rec, root, (0, 0, index, pos), W, p, other_root, other_root[::-1]):
+            if n < 8 or not it.label.startswith("root bit"):
+                items.append(it)
+    want = P.expect(items, W, p)
+    P.assert_covers(want, p)
+    assert want.count(P.OK) >= 64
+    base = np.zeros((1, 2, W, nl), np.uint8)
+    base[0, 0, index] = np.frombuffer(root, np.uint8)
+    got = device_statuses(items, W, S, p, base)
+    bad = [(it.label, it.sample, g, w) for it, g, w in zip(items, got, want) if g != w]
+    assert not bad, (len(bad), bad[:8])
+    # the reference's largest 2k is the limit
+    ctx = R.device_context(0)
+    small = R.DeviceBuffer(4096)
+    smp = (R.Sample * 1)(R.Sample(0, 0, 0, 0))
+    pp = ctypes.byref(p) if p is not None else None
+    assert lib.rsm_proofs_verify_dev(ctx, small.ptr, small.ptr, small.ptr, 65538, S, 1, pp, smp, 1, small.ptr,
+                                     None) == R.RSM_EINVAL
+    small.free()
+
+
+@pytest.mark.parametrize("tree,ns", [("default", 0), ("nmt", 29), ("nmt", 8)])
+def test_guard_bands(lib, tree, ns):
+    """Shares, records, roots and status at 64- but not 128-byte aligned bases between
+    filled bands, the records 2 bytes further: no byte outside d_status[0 .. n) changes
+    and the inputs stay as they were."""
+    W, S = 10, 64
+    p, sq = squares_for(W, S, tree, ns, 1, 77, count=2)
+    items = sq.items(P.picked_samples(W, 3, 2, 40))
+    samples, roots = place(items, committed_roots(sq))
+    n = len(items)
+    assert n % 256 != 0
+    want = P.expect(items, W, p)
+    P.assert_covers(want, p)
+    ctx = R.device_context(0)
+    g_sh = Guarded(np.frombuffer(b"".join(it.share for it in items), np.uint8), 1)
+    g_rec = Guarded(np.frombuffer(b"\x5a\xa5" + b"".join(it.record for it in items), np.uint8), 2)
+    g_roots = Guarded(roots.reshape(-1), 3)
+    g_st = Guarded(np.full(n, 0xDEADBEEF, np.uint32), 4)
+    try:
+        arr = (R.Sample * n)(*[R.Sample(*s) for s in samples])
+        R._check(lib.rsm_proofs_verify_dev(ctx, g_sh.ptr, g_rec.ptr + 2, g_roots.ptr, W, S, roots.shape[0],
+                                           ctypes.byref(p) if p is not None else None, arr, n, g_st.ptr, None))
+        R._check(lib.rsm_sync(ctx))
+        assert list(g_st.result()) == want
+        assert g_sh.unchanged() and g_rec.unchanged() and g_roots.unchanged()
+    finally:
+        for g in (g_sh, g_rec, g_roots, g_st):
+            g.free()
+
+
+def test_argument_errors(lib):
+    ctx = R.device_context(0)
+    W, S = 8, 64
+    buf = R.DeviceBuffer(1 << 16)
+    try:
+        def call(width=W, share_size=S, count=1, p=None, samples=((0, 0, 0, 0),), shares=buf.ptr, n=None):
+            arr = (R.Sample * max(len(samples), 1))(*[R.Sample(*s) for s in samples])
+            return lib.rsm_proofs_verify_dev(ctx, shares, buf.ptr + 1024, buf.ptr + 8192, width, share_size, count,
+                                             ctypes.byref(p) if p is not None else None, arr,
+                                             len(samples) if n is None else n, buf.ptr + 32768, None)
+        assert call() == 0
+        for s in [(1, 0, 0, 0), (0, 2, 0, 0), (0, 0, W, 0), (0, 0, 0, W)]:
+            assert call(samples=((0, 0, 0, 0), s)) == R.RSM_EINVAL
+            assert b"sample 1" in lib.rsm_last_error()
+        assert call(shares=buf.ptr + 8) == R.RSM_EINVAL  # d_shares must be 16-byte aligned
+        assert call(share_size=96) == R.RSM_ESHARESIZE
+        assert call(n=0) == 0 and call(count=0) == 0
+        assert call(width=0) == R.RSM_EINVAL and call(width=65537) == R.RSM_EINVAL
+        assert call(width=65536, samples=((0, 1, 65535, 65535),), n=0) == 0
+        assert call(p=R.NmtParams(0, 1, 4)) == R.RSM_EINVAL and call(p=R.NmtParams(33, 1, 4)) == R.RSM_EINVAL
+        assert call(p=R.NmtParams(29, 1, 4), share_size=0) == R.RSM_ETREE
+        assert call(n=(1 << 24) + 1) == R.RSM_EINVAL
+        R._check(lib.rsm_sync(ctx))
+    finally:
+        buf.free()
+
+
+@pytest.mark.parametrize("tree", ["default", "nmt"])
+def test_serve_verify_import_repair(lib, tree):
+    """The loop a reconstructing node runs: proofs served from one square, verified
+    against the committed roots and imported into an empty one, then Repair."""
+    k, S, ns = 8, 64, 29
+    W = 2 * k
+    ods = V.sorted_q0_square(k, S, ns, 2024)[:k, :k]
+    ctor = R.NewDefaultTree if tree == "default" else R.newErasuredNamespacedMerkleTreeConstructor(k, ns)
+    codec = R.NewLeoRSCodec()
+    eds = R.ComputeExtendedDataSquare([ods[r, c].tobytes() for r in range(k) for c in range(k)], codec, ctor)
+    rr, cr = eds.RowRoots(), eds.ColRoots()
+    flat = eds.Flattened()
+    # quadrant 0 by row proofs, a few more cells by column proofs; three proofs are
+    # tampered with, and each of their rows has one of the extra cells to stay decodable
+    tampered = {(1, 2): "share", (4, 4): "node", (6, 0): "pos"}
+    extra = [(1, k + 3), (4, k), (6, W - 1), (k + 2, 5), (W - 1, W - 1)]
+    cells = [(r, c) for r in range(k) for c in range(k)]
+    proofs = eds.Proofs([(R.Row, r, c) for r, c in cells] + [(R.Col, c, r) for r, c in extra])
+    batch = []
+    for (r, c), pr in zip(cells + extra, proofs):
+        axis, index, pos = (R.Row, r, c) if (r, c) in cells else (R.Col, c, r)
+        how = tampered.get((r, c)) if axis == R.Row else None
+        if how == "share":
+            pr.share = pr.share[:-1] + bytes([pr.share[-1] ^ 1])
+        elif how == "node":
+            pr.nodes[2] = pr.nodes[2][:-1] + bytes([pr.nodes[2][-1] ^ 0x80])
+        elif how == "pos":
+            pos = 2  # a valid proof of leaf 0 presented as leaf 2
+        batch.append((axis, index, pos, pr))
+    # on the CPU: the untampered samples alone leave the square repairable
+    keep = {(r, c) for r, c in cells + extra if (r, c) not in tampered}
+    plain = crossword.Square(flat)
+    masked = [flat[r * W + c] if (r, c) in keep else None for r in range(W) for c in range(W)]
+    assert crossword.repair(masked, plain.roots(crossword.Row), plain.roots(crossword.Col)) == flat
+    host = R.NewExtendedDataSquare(codec, ctor, W, S)
+    want = host.SetCellsVerified(rr, cr, batch, device=False)  # the context-free path
+    assert sorted(i for i, s in enumerate(want) if s) == sorted(cells.index(rc) for rc in tampered)
+    assert [want[cells.index(rc)] for rc in tampered] == [P.ROOT, P.ROOT, P.MALFORMED]
+    got_sq = R.NewExtendedDataSquare(codec, ctor, W, S)
+    assert got_sq.SetCellsVerified(rr, cr, batch) == want
+    assert got_sq.Flattened() == host.Flattened() == masked
+    assert got_sq.SetCellsVerified(rr, cr, batch[:5]) == [P.OCCUPIED] * 5
+    got_sq.Repair(rr, cr)
+    assert got_sq.Equals(eds)
