@@ -388,6 +388,93 @@ int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t 
 int rsm_nmt_tree_verify(const rsm_nmt_params* params, uint32_t index, const uint8_t* share, uint32_t share_size,
                         uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root, uint32_t* status);
 
+/* ---- namespace proofs -------------------------------------------------------------- */
+/* "Every share of namespace nid in this row (or column), with proof that these are all
+ * of them": nmt's ProveNamespace / VerifyNamespace (celestia-node's GetSharesByNamespace
+ * asks it of every row), restated in the level picture above.  NMT only.
+ *
+ * Vector: row (axis 0) or column (axis 1) `index` of a [W][W][S] square, W = 2 *
+ * square_size.  Leaf p carries the namespace the wrapper pushes: share[:namespace_size]
+ * when p < square_size and index < square_size, else 0xFF..; namespaces compare as
+ * big-endian byte strings.  Kind of the answer, the first rule that applies: */
+#define RSM_NS_EMPTY 0     /* nid < root.min or nid > root.max (the root as stored, so
+                              ignore_max_namespace is applied: 0xFF.. is EMPTY in a quadrant-0
+                              row).  start = end = 0, no nodes, no shares */
+#define RSM_NS_INCLUSION 1 /* start = first leaf >= nid, end = first leaf > nid, start < end:
+                              the range proof of [start, end); shares = leaves start .. end-1 */
+#define RSM_NS_ABSENCE 2   /* no such leaf though nid lies in the root's range: the range
+                              proof of [start, start + 1), the first leaf above nid, whose node
+                              ns || ns || digest the record carries; end = start + 1, no shares */
+#define RSM_NS_TREE 3      /* device only, checked first: the tree's status word is non-zero
+                              (push order), nothing is searched.  start = end = 0, no nodes */
+/* Range proof of [start, end), from (W, start, end) alone: with a = start, last = end - 1,
+ * level l = 0 .. L-1 gives the left node (l, a - 1) when a is odd and the right node
+ * (l, last + 1) when last is even and last + 1 < ceil(W / 2^l); then a >>= 1, last >>= 1.
+ * Record order: the left nodes from the top level down, then the right nodes from the
+ * bottom level up (nmt's Proof.Nodes: an in-order walk of the RFC 6962 split).
+ * Record, little-endian, fixed stride rsm_ns_record_bytes = 16 + (2L + 1) * node_len,
+ * node_len = 2 * namespace_size + 32:
+ *   uint32 kind | uint32 start | uint32 end | uint32 n_nodes | n_nodes nodes | zeros up to
+ *   slot 2L | slot 2L: the leaf node (ABSENCE only, else zeros)
+ * Node bytes min || max || digest as in roots; a level-0 node has the leaf's namespace as
+ * both. */
+typedef struct {
+    uint32_t square; /* square of a batch */
+    uint32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */
+    uint32_t index;  /* row or column */
+} rsm_ns_query;
+/* Bytes of one namespace proof record (0 for width 0, no params or a namespace size 0). */
+uint32_t rsm_ns_record_bytes(uint32_t width, const rsm_nmt_params* nmt);
+/* n namespace proofs out of an NMT node store.  d_nodes / d_status: what
+ * rsm_proof_nodes_dev wrote for these `count` squares (both required); d_eds: the squares
+ * (needed with d_shares).  `queries` and `nids` ([n][namespace_size]) are HOST memory,
+ * validated before anything is enqueued (RSM_EINVAL names the first query with
+ * square >= count, axis > 1 or index >= width) and copied before the call returns;
+ * n <= 2^20.  d_records (device, any alignment) receives n records; d_offsets (device,
+ * 4-byte aligned, n + 1 uint32) the exclusive prefix sum of the queries' share counts,
+ * d_offsets[n] the total; d_shares (device, nullable, 16-byte aligned like d_eds) the
+ * shares packed query after query, query i at share d_offsets[i] -- written only where
+ * d_offsets[i + 1] <= shares_cap (shares), so a caller compares d_offsets[n] with its
+ * capacity and calls again with a larger buffer.  Nothing is stored past shares_cap
+ * shares, n records or n + 1 offsets.  nmt == NULL (the DefaultTree has no namespaces)
+ * and shapes beyond the NMT node store's limits: RSM_EUNSUPPORTED.  n == 0 or count == 0
+ * launches nothing.  Asynchronous on `stream`. */
+int rsm_ns_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status, const void* d_eds, uint32_t width,
+                      uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt, const rsm_ns_query* queries,
+                      const uint8_t* nids, uint32_t n, void* d_records, void* d_offsets, void* d_shares,
+                      uint64_t shares_cap, void* stream);
+/* Host restatement (merkle.cpp), any n_leaves >= 1: the record of namespace `nid`
+ * (namespace_size bytes) in the vector `leaves` into record_out
+ * (rsm_ns_record_bytes(n_leaves, ..)), the root into root_out (nullable); the shares of
+ * an inclusion proof are leaves[start .. end).  RSM_ETREE where the tree fails, as
+ * rsm_nmt_tree_prove (so kind 3 never leaves this function). */
+int rsm_nmt_namespace_prove(const rsm_nmt_params* params, uint32_t index, const uint8_t* const* leaves,
+                            uint32_t n_leaves, uint32_t leaf_size, const uint8_t* nid, uint8_t* record_out,
+                            uint8_t* root_out);
+/* Verification of a namespace proof (host only): `shares` [n_shares][share_size] are the
+ * shares presented with `record` for namespace `nid` of vector `index`, `root` the
+ * committed root of the tree of n_leaves leaves.  *status, the first that applies: */
+#define RSM_PROOF_NAMESPACE 5  /* INCLUSION: a leaf's wrapper namespace differs from nid;
+                                  ABSENCE: the leaf node has min != max or min <= nid */
+#define RSM_PROOF_INCOMPLETE 6 /* a left node with max >= nid or a right node with min <= nid
+                                  (shares were left out); EMPTY though root.min <= nid <= root.max */
+/* 1 RSM_PROOF_MALFORMED: kind not 0..2; EMPTY with a non-zero start, end, n_nodes or with
+ *   shares; INCLUSION unless start < end <= n_leaves and n_shares == end - start; ABSENCE
+ *   unless end == start + 1 <= n_leaves and n_shares == 0; n_nodes differs from the count
+ *   (n_leaves, start, end) dictates.
+ * 5 RSM_PROOF_NAMESPACE, 6 RSM_PROOF_INCOMPLETE as above.
+ * 2 RSM_PROOF_ORDER: a fold step has right.min < left.max.
+ * 3 RSM_PROOF_ROOT: the fold differs from the root (all of min || max || digest).
+ * Positions are bound as for single shares: counts and operand sides come from
+ * (n_leaves, start, end) once the header passed the MALFORMED check, the fold runs over
+ * the derived count, record bytes past the derived nodes (and, for ABSENCE, the leaf
+ * slot) are never read, and no address depends on record or share contents.  The return
+ * value is an argument error only (RSM_EINVAL; RSM_ETREE for shares shorter than the
+ * namespace). */
+int rsm_nmt_namespace_verify(const rsm_nmt_params* params, uint32_t index, const uint8_t* nid, const uint8_t* shares,
+                             uint32_t n_shares, uint32_t share_size, uint32_t n_leaves, const uint8_t* record,
+                             const uint8_t* root, uint32_t* status);
+
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */
 int rsm_eds_compute(rsm_ctx* ctx, const uint8_t* const* data, const uint32_t* lens, uint64_t n,
@@ -429,6 +516,20 @@ int rsm_eds_roots(rsm_eds* eds, int axis, rsm_tree_root_fn tree_fn, void* user, 
  * on the path. */
 int rsm_eds_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
                    uint8_t* records_out, uint8_t* shares_out);
+
+/* Namespace proofs of `nid` (namespace_size bytes) in rows (axis 0) or columns (axis 1)
+ * indices[0 .. n) of this square: n records of rsm_ns_record_bytes(width, nmt) into
+ * records_out, offsets_out[n + 1] and the packed shares into shares_out (nullable,
+ * room for shares_cap shares) as rsm_ns_proofs_dev writes them -- vector i's shares only
+ * where offsets_out[i + 1] <= shares_cap.  tree_fn / user must be rsm_nmt_tree_root with
+ * its params (anything else RSM_EUNSUPPORTED).  RSM_EINVAL for an index out of range,
+ * RSM_ETREE for a vector that is incomplete or whose tree fails.  With a context and a
+ * complete square of a supported width the cached node store of rsm_eds_proofs is reused
+ * or built and one rsm_ns_proofs_dev call answers; otherwise the host restatement runs
+ * per vector.  Results never depend on the path. */
+int rsm_eds_namespace_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, int axis, const uint32_t* indices,
+                             uint32_t n, const uint8_t* nid, uint8_t* records_out, uint32_t* offsets_out,
+                             uint8_t* shares_out, uint64_t shares_cap);
 
 /* Rebuilding a square from sampled shares: verifies n samples (square = 0; shares
  * [n][share size], records [n][rsm_proof_record_bytes(width, nmt)]) against the

@@ -208,6 +208,13 @@ SIGNATURES = {
     "rsm_default_tree_verify": (_I32, [_VP, _U32, _U32, _U32, _VP, _VP, ctypes.POINTER(_U32)]),
     "rsm_nmt_tree_verify": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _U32, _VP, _VP,
                                    ctypes.POINTER(_U32)]),
+    "rsm_ns_record_bytes": (_U32, [_U32, ctypes.POINTER(NmtParams)]),
+    "rsm_ns_proofs_dev": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP, _U32, _VP, _VP,
+                                 _VP, _U64, _VP]),
+    "rsm_nmt_namespace_prove": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _VP, _VP, _VP]),
+    "rsm_nmt_namespace_verify": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _VP, _U32, _U32, _U32, _VP, _VP,
+                                        ctypes.POINTER(_U32)]),
+    "rsm_eds_namespace_proofs": (_I32, [_VP, _VP, _VP, _I32, _VP, _U32, _VP, _VP, _VP, _VP, _U64]),
     "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
 }
 
@@ -727,6 +734,125 @@ def verify_samples_dev(shares: "DeviceBuffer", records: "DeviceBuffer", roots: "
 
 
 # ---------------------------------------------------------------------------
+# Namespace proofs (include/rsmt2d_hip.h "namespace proofs")
+# ---------------------------------------------------------------------------
+#: NamespaceProof.kind
+NS_EMPTY, NS_INCLUSION, NS_ABSENCE, NS_TREE = 0, 1, 2, 3
+
+
+class NsQuery(ctypes.Structure):
+    """rsm_ns_query: row (axis 0) / column (axis 1) ``index`` of ``square``."""
+    _fields_ = [("square", ctypes.c_uint32), ("axis", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+
+class NamespaceProof:
+    """Every share of one namespace in a row or column, with the proof that these are
+    all of them (nmt's ProveNamespace).
+
+    ``kind``: NS_EMPTY (the namespace lies outside the root's range: nothing to show),
+    NS_INCLUSION (``shares`` are leaves ``start`` .. ``end - 1``), NS_ABSENCE
+    (``leaf_node`` is the node of leaf ``start``, the first one above the namespace) or
+    NS_TREE (device batches only: the tree fails, there is no proof).  ``nodes``: the
+    range proof of [start, end) in nmt's ``Proof.Nodes`` order.  ``numLeaves``,
+    ``nmt``, ``tree_index``: the tree, as in ``Proof``."""
+
+    def __init__(self, kind: int, start: int, end: int, nodes: List[bytes], leaf_node: Optional[bytes],
+                 shares: List[bytes], numLeaves: int, nmt: NmtParams, tree_index: int = 0):
+        self.kind, self.start, self.end, self.nodes = kind, start, end, nodes
+        self.leaf_node, self.shares = leaf_node, shares
+        self.numLeaves, self.nmt, self.tree_index = numLeaves, nmt, tree_index
+
+    def record(self) -> bytes:
+        """The namespace proof record (include/rsmt2d_hip.h): u32 kind | start | end |
+        n_nodes | the nodes | zeros up to slot 2L | the leaf node or zeros."""
+        nl = 2 * int(self.nmt.namespace_size) + 32
+        levels = (self.numLeaves - 1).bit_length()
+        if len(self.nodes) > 2 * levels or any(len(nd) != nl for nd in self.nodes) or \
+                (self.leaf_node is not None and len(self.leaf_node) != nl):
+            raise RSMError(RSM_EINVAL, "proof nodes do not fit the tree's record")
+        head = b"".join(int(v).to_bytes(4, "little") for v in (self.kind, self.start, self.end, len(self.nodes)))
+        body = b"".join(self.nodes)
+        return head + body + bytes(2 * levels * nl - len(body)) + (self.leaf_node or bytes(nl))
+
+    def verify(self, root: bytes, nid: bytes) -> int:
+        """The RSM_PROOF_* status of this proof for namespace ``nid`` against the
+        committed ``root`` (rsm_nmt_namespace_verify): 0 = these are all the shares."""
+        ns = int(self.nmt.namespace_size)
+        if len(nid) != ns or len(root) != 2 * ns + 32:
+            raise RSMError(RSM_EINVAL, "namespace or root of the wrong length")
+        S = len(self.shares[0]) if self.shares else 0
+        if any(len(sh) != S for sh in self.shares):
+            raise RSMError(RSM_EINVAL, "shares of different sizes")
+        st = ctypes.c_uint32(0)
+        _check(library().rsm_nmt_namespace_verify(ctypes.byref(self.nmt), self.tree_index, bytes(nid),
+                                                  b"".join(self.shares), len(self.shares), S, self.numLeaves,
+                                                  self.record(), bytes(root), ctypes.byref(st)))
+        return int(st.value)
+
+
+def _parse_ns_records(rec: bytes, offsets, shares: Optional[bytes], indices, width: int, S: int,
+                      nmt: NmtParams) -> List[NamespaceProof]:
+    """NamespaceProof objects from n records, the n + 1 offsets and the packed shares."""
+    nl = 2 * int(nmt.namespace_size) + 32
+    levels = (width - 1).bit_length()
+    rb = 16 + (2 * levels + 1) * nl
+    out = []
+    for i, index in enumerate(indices):
+        r = rec[i * rb:(i + 1) * rb]
+        kind, start, end, n_nodes = (int.from_bytes(r[4 * j:4 * j + 4], "little") for j in range(4))
+        nodes = [r[16 + j * nl: 16 + (j + 1) * nl] for j in range(n_nodes)]
+        leaf = r[16 + 2 * levels * nl:] if kind == NS_ABSENCE else None
+        sh = [shares[p * S:(p + 1) * S] for p in range(int(offsets[i]), int(offsets[i + 1]))]
+        out.append(NamespaceProof(kind, start, end, nodes, leaf, sh, width, nmt, index))
+    return out
+
+
+def prove_namespaces_dev(buf: "DeviceBuffer", width: int, share_size: int, queries: Sequence[tuple],
+                         nids: Sequence[bytes], nmt: NmtParams, count: int = 1) -> List[NamespaceProof]:
+    """Namespace proofs of ``(square, axis, index)`` queries, query i for namespace
+    ``nids[i]``, of ``count`` complete device-resident [width][width][share_size] squares
+    in ``buf``: one node-store build (rsm_proof_nodes_dev), then rsm_ns_proofs_dev once
+    for the records and the share total and once more with a share buffer of that size."""
+    import numpy as np
+    L, ctx, n = library(), buf.ctx, len(queries)
+    if nmt is None:
+        raise RSMError(RSM_EUNSUPPORTED, "namespace proofs need the NMT")
+    p, ns = ctypes.byref(nmt), int(nmt.namespace_size)
+    if len(nids) != n or any(len(x) != ns for x in nids):
+        raise RSMError(RSM_EINVAL, "one namespace of namespace_size bytes per query")
+    nbytes = int(L.rsm_proof_nodes_bytes(width, p, count))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device proofs: {count} squares of width {width} not supported")
+    if n == 0:
+        return []
+    rb = int(L.rsm_ns_record_bytes(width, p))
+    bufs = [DeviceBuffer(nbytes), DeviceBuffer(count * 2 * width * 4), DeviceBuffer(n * rb), DeviceBuffer((n + 1) * 4)]
+    nodes, status, recs, offs = bufs
+    try:
+        arr = (NsQuery * n)(*[NsQuery(*q) for q in queries])
+        flat = b"".join(bytes(x) for x in nids)
+        _check(L.rsm_proof_nodes_dev(ctx, buf.ptr, width, share_size, count, p, nodes.ptr, None, status.ptr, None))
+        _check(L.rsm_ns_proofs_dev(ctx, nodes.ptr, status.ptr, buf.ptr, width, share_size, count, p, arr, flat, n,
+                                   recs.ptr, offs.ptr, None, 0, None))
+        _check(L.rsm_sync(ctx))
+        offsets = offs.download((n + 1) * 4).view(np.uint32).copy()
+        total = int(offsets[n])
+        sh = b""
+        if total:
+            shs = DeviceBuffer(total * share_size)
+            bufs.append(shs)
+            _check(L.rsm_ns_proofs_dev(ctx, nodes.ptr, status.ptr, buf.ptr, width, share_size, count, p, arr, flat, n,
+                                       recs.ptr, offs.ptr, shs.ptr, total, None))
+            _check(L.rsm_sync(ctx))
+            sh = shs.download(total * share_size).tobytes()
+        rec = recs.download(n * rb).tobytes()
+    finally:
+        for b in bufs:
+            b.free()
+    return _parse_ns_records(rec, offsets, sh, [q[2] for q in queries], width, share_size, nmt)
+
+
+# ---------------------------------------------------------------------------
 # ExtendedDataSquare (extendeddatasquare.go)
 # ---------------------------------------------------------------------------
 class ExtendedDataSquare:
@@ -870,6 +996,39 @@ class ExtendedDataSquare:
     def ColProof(self, rowIdx: int, colIdx: int) -> "Proof":
         """Share (rowIdx, colIdx) with its proof against ColRoots()[colIdx]."""
         return self.Proofs([(Col, colIdx, rowIdx)])[0]
+
+    # --- namespace proofs (rsm_eds_namespace_proofs) ---
+    def NamespaceProofs(self, nid: bytes, axis: int = 0, indices: Optional[Sequence[int]] = None) -> List["NamespaceProof"]:
+        """The shares of namespace ``nid`` in each of rows (``axis`` = Row, the default)
+        or columns (Col) ``indices`` (all of them by default), each with the proof that they are all of that vector's
+        (nmt's ProveNamespace; verify with ``NamespaceProof.verify`` against
+        RowRoots() / ColRoots()).  NMT squares only.  A complete square with a device
+        context answers from its cached tree nodes on the GPU; anything else runs the
+        host trees."""
+        tf = self._tree_fn
+        if not isinstance(tf, ErasuredNamespacedMerkleTreeConstructor):
+            raise RSMError(RSM_EUNSUPPORTED, "namespace proofs are built for the NMT only")
+        keep, fn, user = _tree_callback(tf)
+        nmt = tf.params
+        if len(nid) != int(nmt.namespace_size):
+            raise RSMError(RSM_EINVAL, "a namespace of namespace_size bytes is needed")
+        L, w, S = library(), self.Width(), self.shareSize
+        indices = list(range(w)) if indices is None else [int(i) for i in indices]
+        n = len(indices)
+        rb = int(L.rsm_ns_record_bytes(max(w, 1), ctypes.byref(nmt)))
+        idx = (ctypes.c_uint32 * max(n, 1))(*indices)
+        rec = ctypes.create_string_buffer(max(n * rb, 1))
+        offs = (ctypes.c_uint32 * (n + 1))()
+        cap = n * w  # a vector has at most w shares of any namespace
+        sh = ctypes.create_string_buffer(max(cap * S, 1))
+        _check(L.rsm_eds_namespace_proofs(self._h, fn, user, axis, idx, n, bytes(nid), rec, offs, sh, cap))
+        return _parse_ns_records(rec.raw, list(offs), sh.raw, indices, w, S, nmt)
+
+    def NamespaceData(self, nid: bytes) -> List[tuple]:
+        """``(rowIdx, NamespaceProof)`` for every row whose proof for ``nid`` is not
+        NS_EMPTY: the answer to celestia-node's GetSharesByNamespace."""
+        proofs = self.NamespaceProofs(nid, Row)
+        return [(r, pr) for r, pr in enumerate(proofs) if pr.kind != NS_EMPTY]
 
     def SetCellsVerified(self, rowRoots: Sequence[bytes], colRoots: Sequence[bytes], proofs: Sequence[tuple],
                          device: bool = True) -> List[int]:

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "proof_node.hpp"
 #include "rsm_kernels.hpp"
 
 namespace rsm {
@@ -27,21 +28,15 @@ namespace {
 
 typedef uint32_t pv4u __attribute__((ext_vector_type(4)));
 
-// byte i of a big-endian word array
-__device__ __forceinline__ uint8_t word_byte(const uint32_t* w, uint32_t i) {
-    return (uint8_t)(w[i >> 2] >> (24u - 8u * (i & 3u)));
-}
-
 __global__ __launch_bounds__(256) void proof_gather_kernel(const uint32_t* __restrict__ store, uint32_t W,
                                                            uint32_t squares, uint32_t ns,
                                                            const ProofSample* __restrict__ samples, uint32_t n,
                                                            uint8_t* __restrict__ records) {
-    const uint32_t L = proof_levels(W), U = proof_tree_nodes(W);
+    const uint32_t L = proof_levels(W);
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n * L) return;
     const uint32_t s = t / L, l = t - s * L;
     const ProofSample sm = samples[s];
-    const uint32_t lw = ns ? kProofNmtLeafWords : kProofShaWords, nw = ns ? kProofNmtNodeWords : kProofShaWords;
     const uint32_t node_len = ns ? 2 * ns + 32 : 32;
     uint8_t* rec = records + (uint64_t)s * (8u + L * node_len);
     // slots below this level's, the record's node count and the operand sides
@@ -70,31 +65,7 @@ __global__ __launch_bounds__(256) void proof_gather_kernel(const uint32_t* __res
         for (uint32_t i = 0; i < node_len; ++i) out[i] = 0;
         return;
     }
-    const uint32_t sib = (sm.pos >> l) ^ 1u;
-    const uint32_t *mn, *mx, *dg;  // the node's min / max namespace and digest words
-    if (l == 0) {
-        const uint64_t cell = sm.axis == 0 ? (uint64_t)sm.index * W + sib : (uint64_t)sib * W + sm.index;
-        const uint32_t* p = store + ((uint64_t)sm.square * W * W + cell) * lw;
-        mn = mx = p;  // a leaf's namespace is both
-        dg = ns ? p + 8 : p;
-    } else {
-        const uint64_t tree = (uint64_t)sm.square * 2 * W + (uint64_t)sm.axis * W + sm.index;
-        const uint32_t* p = store + (uint64_t)squares * W * W * lw + (tree * U + proof_level_offset(W, l) + sib) * nw;
-        mn = p;
-        mx = p + 8;
-        dg = ns ? p + 16 : p;
-    }
-    for (uint32_t i = 0; i < ns; ++i) {
-        out[i] = word_byte(mn, i);
-        out[ns + i] = word_byte(mx, i);
-    }
-    out += 2 * ns;
-    if ((reinterpret_cast<uintptr_t>(out) & 3u) == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) reinterpret_cast<uint32_t*>(out)[i] = __builtin_bswap32(dg[i]);
-    } else {
-        for (uint32_t i = 0; i < 32; ++i) out[i] = word_byte(dg, i);
-    }
+    store_node_bytes(store, W, squares, ns, sm.square, sm.axis, sm.index, l, (sm.pos >> l) ^ 1u, out);
 }
 
 __global__ __launch_bounds__(256) void share_gather_kernel(const uint8_t* __restrict__ eds, uint32_t W, uint32_t S,

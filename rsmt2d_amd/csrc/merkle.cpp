@@ -485,20 +485,19 @@ extern "C" int rsm_default_tree_prove(const uint8_t* const* leaves, uint32_t n_l
     return RSM_OK;
 }
 
-extern "C" int rsm_nmt_tree_prove(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves,
-                                  uint32_t n_leaves, uint32_t leaf_size, uint32_t pos, uint8_t* record_out,
-                                  uint8_t* root_out) {
-    if (!p || !leaves || !record_out || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
-        pos >= n_leaves)
-        return RSM_EINVAL;
+namespace {
+
+// Level 0 of the erasured NMT over `leaves` (erasuredNamespacedMerkleTree.Push, as
+// rsm_nmt_tree_root): n_leaves nodes ns || ns || H(0x00 || ns || share) in `lvl`.
+int nmt_leaf_level(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves, uint32_t n_leaves,
+                   uint32_t leaf_size, std::vector<uint8_t>& lvl) {
     const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32;
-    const bool ig = p->ignore_max_namespace != 0;
-    // erasuredNamespacedMerkleTree.Push, as rsm_nmt_tree_root
     if (index + 1 > 2 * k || n_leaves > 2 * k) return RSM_ETREE;
     if (leaf_size < nsz) return RSM_ETREE;
     std::vector<uint8_t> parity(nsz, 0xFF);
     const size_t ML = (size_t)nsz + leaf_size;
-    std::vector<uint8_t> msg((size_t)n_leaves * ML), lvl((size_t)n_leaves * NB);
+    std::vector<uint8_t> msg((size_t)n_leaves * ML);
+    lvl.assign((size_t)n_leaves * NB, 0);
     const uint8_t* prev = nullptr;
     for (uint32_t i = 0; i < n_leaves; ++i) {
         if (!leaves[i]) return RSM_ETREE;
@@ -518,20 +517,40 @@ extern "C" int rsm_nmt_tree_prove(const rsm_nmt_params* p, uint32_t index, const
         hash_prefixed(0x00, m, c, (uint32_t)ML, dg);
         for (int q = 0; q < c; ++q) memcpy(&lvl[(size_t)(i + q) * NB + 2 * nsz], dg[q].b, 32);
     }
-    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) {
-        for (uint32_t j = 0; j < np; j += kHashBatch) {
-            const int c = (int)std::min<uint32_t>(kHashBatch, np - j);
-            const uint8_t* m[kHashBatch];
-            for (int q = 0; q < c; ++q) {
-                const uint8_t* l = cur + (size_t)(2 * (j + q)) * NB;
-                if (!nmt_pair(l, l + NB, nsz, ig, out + (size_t)(j + q) * NB)) return false;
-                m[q] = l;
-            }
-            hash_prefixed(0x01, m, c, 2 * NB, dg);
-            for (int q = 0; q < c; ++q) memcpy(out + (size_t)(j + q) * NB + 2 * nsz, dg[q].b, 32);
+    return RSM_OK;
+}
+
+// HashNode of pairs 0 .. np-1 of the level `cur` into `out`; false: unordered siblings
+bool nmt_join_pairs(const uint8_t* cur, uint32_t np, uint8_t* out, uint32_t nsz, bool ig) {
+    const uint32_t NB = 2 * nsz + 32;
+    Digest dg[kHashBatch];
+    for (uint32_t j = 0; j < np; j += kHashBatch) {
+        const int c = (int)std::min<uint32_t>(kHashBatch, np - j);
+        const uint8_t* m[kHashBatch];
+        for (int q = 0; q < c; ++q) {
+            const uint8_t* l = cur + (size_t)(2 * (j + q)) * NB;
+            if (!nmt_pair(l, l + NB, nsz, ig, out + (size_t)(j + q) * NB)) return false;
+            m[q] = l;
         }
-        return true;
-    };
+        hash_prefixed(0x01, m, c, 2 * NB, dg);
+        for (int q = 0; q < c; ++q) memcpy(out + (size_t)(j + q) * NB + 2 * nsz, dg[q].b, 32);
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int rsm_nmt_tree_prove(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves,
+                                  uint32_t n_leaves, uint32_t leaf_size, uint32_t pos, uint8_t* record_out,
+                                  uint8_t* root_out) {
+    if (!p || !leaves || !record_out || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
+        pos >= n_leaves)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    std::vector<uint8_t> lvl;
+    if (int rc = nmt_leaf_level(p, index, leaves, n_leaves, leaf_size, lvl)) return rc;
+    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) { return nmt_join_pairs(cur, np, out, nsz, ig); };
     if (!prove_levels(lvl, n_leaves, NB, pos, record_out, join)) return RSM_ETREE;
     if (root_out) memcpy(root_out, lvl.data(), NB);
     return RSM_OK;
@@ -641,4 +660,185 @@ extern "C" int rsm_nmt_tree_verify(const rsm_nmt_params* p, uint32_t index, cons
     }
     *status = memcmp(acc.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
     return RSM_OK;
+}
+
+// ---- namespace proofs (include/rsmt2d_hip.h "namespace proofs") ----
+// Host restatements of kernels_nsproof.hip: the same range [start, end) and the same
+// range-proof nodes, by levels, out of a tree built here instead of a node store; and
+// the verifier, which derives counts and operand sides from (n_leaves, start, end).
+namespace {
+
+struct RangeNode {
+    uint32_t level, j;
+};
+
+// The range proof's nodes of [start, end) of n leaves in record order: the left nodes
+// from the top level down, then the right nodes from the bottom level up.
+std::vector<RangeNode> range_nodes(uint32_t n, uint32_t start, uint32_t end, uint32_t* n_left) {
+    std::vector<RangeNode> left, right;
+    uint32_t a = start, last = end - 1;
+    for (uint32_t l = 0, L = proof_levels_of(n); l < L; ++l) {
+        const uint32_t cnt = (uint32_t)(((uint64_t)n + (1ull << l) - 1) >> l);
+        if (a & 1u) left.push_back({l, a - 1});
+        if (!(last & 1u) && last + 1 < cnt) right.push_back({l, last + 1});
+        a >>= 1;
+        last >>= 1;
+    }
+    *n_left = (uint32_t)left.size();
+    std::vector<RangeNode> out(left.rbegin(), left.rend());
+    out.insert(out.end(), right.begin(), right.end());
+    return out;
+}
+
+void put_le32(uint8_t* p, uint32_t v) {
+    for (int b = 0; b < 4; ++b) p[b] = (uint8_t)(v >> (8 * b));
+}
+uint32_t get_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+}  // namespace
+
+extern "C" uint32_t rsm_ns_record_bytes(uint32_t width, const rsm_nmt_params* nmt) {
+    if (width == 0 || !nmt || nmt->namespace_size == 0) return 0;
+    return 16 + (2 * proof_levels_of(width) + 1) * (2 * nmt->namespace_size + 32);
+}
+
+extern "C" int rsm_nmt_namespace_prove(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves,
+                                       uint32_t n_leaves, uint32_t leaf_size, const uint8_t* nid, uint8_t* record_out,
+                                       uint8_t* root_out) {
+    if (!p || !leaves || !nid || !record_out || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32, L = proof_levels_of(n_leaves);
+    const bool ig = p->ignore_max_namespace != 0;
+    std::vector<std::vector<uint8_t>> lv(L + 1);  // every level of the tree
+    if (int rc = nmt_leaf_level(p, index, leaves, n_leaves, leaf_size, lv[0])) return rc;
+    for (uint32_t l = 0, cnt = n_leaves; l < L; ++l) {
+        const uint32_t np = cnt / 2, up = (cnt + 1) / 2;
+        lv[l + 1].assign((size_t)up * NB, 0);
+        if (!nmt_join_pairs(lv[l].data(), np, lv[l + 1].data(), nsz, ig)) return RSM_ETREE;
+        if (cnt & 1u) memcpy(&lv[l + 1][(size_t)np * NB], &lv[l][(size_t)(cnt - 1) * NB], NB);
+        cnt = up;
+    }
+    const uint8_t* root = lv[L].data();
+    if (root_out) memcpy(root_out, root, NB);
+    memset(record_out, 0, rsm_ns_record_bytes(n_leaves, p));
+    if (memcmp(nid, root, nsz) < 0 || memcmp(nid, root + nsz, nsz) > 0) return RSM_OK;  // RSM_NS_EMPTY: all zeros
+    uint32_t start = 0, end;
+    while (start < n_leaves && memcmp(&lv[0][(size_t)start * NB], nid, nsz) < 0) ++start;
+    for (end = start; end < n_leaves && memcmp(&lv[0][(size_t)end * NB], nid, nsz) == 0;) ++end;
+    if (start >= n_leaves) return RSM_OK;  // unreachable on a tree that passed: root.max is a leaf's
+    const bool absent = start == end;
+    if (absent) {
+        end = start + 1;
+        memcpy(record_out + 16 + (size_t)2 * L * NB, &lv[0][(size_t)start * NB], NB);
+    }
+    uint32_t n_left;
+    const std::vector<RangeNode> nodes = range_nodes(n_leaves, start, end, &n_left);
+    put_le32(record_out, absent ? RSM_NS_ABSENCE : RSM_NS_INCLUSION);
+    put_le32(record_out + 4, start);
+    put_le32(record_out + 8, end);
+    put_le32(record_out + 12, (uint32_t)nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i)
+        memcpy(record_out + 16 + i * NB, &lv[nodes[i].level][(size_t)nodes[i].j * NB], NB);
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_namespace_verify(const rsm_nmt_params* p, uint32_t index, const uint8_t* nid,
+                                        const uint8_t* shares, uint32_t n_shares, uint32_t share_size,
+                                        uint32_t n_leaves, const uint8_t* record, const uint8_t* root,
+                                        uint32_t* status) {
+    if (!p || !nid || !record || !root || !status || (n_shares && !shares) || p->namespace_size == 0 ||
+        p->square_size == 0 || n_leaves == 0)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32, L = proof_levels_of(n_leaves);
+    const bool ig = p->ignore_max_namespace != 0;
+    if (n_shares && share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
+    const uint32_t kind = get_le32(record), start = get_le32(record + 4), end = get_le32(record + 8),
+                   n_nodes = get_le32(record + 12);
+    auto done = [&](uint32_t s) {
+        *status = s;
+        return RSM_OK;
+    };
+    // 1. the header against what (n_leaves, start, end) dictates
+    if (kind == RSM_NS_EMPTY) {
+        if (start || end || n_nodes || n_shares) return done(RSM_PROOF_MALFORMED);
+        const bool covered = memcmp(root, nid, nsz) <= 0 && memcmp(nid, root + nsz, nsz) <= 0;
+        return done(covered ? RSM_PROOF_INCOMPLETE : RSM_PROOF_OK);
+    }
+    if (kind == RSM_NS_INCLUSION) {
+        if (!(start < end && end <= n_leaves) || n_shares != end - start) return done(RSM_PROOF_MALFORMED);
+    } else if (kind == RSM_NS_ABSENCE) {
+        if (start >= n_leaves || end != start + 1 || n_shares != 0) return done(RSM_PROOF_MALFORMED);
+    } else {
+        return done(RSM_PROOF_MALFORMED);
+    }
+    uint32_t n_left;
+    const std::vector<RangeNode> shape = range_nodes(n_leaves, start, end, &n_left);
+    if (n_nodes != shape.size()) return done(RSM_PROOF_MALFORMED);
+    // 2. the leaves carry nid / the absence leaf is one leaf above nid
+    std::vector<uint8_t> cur((size_t)(end - start) * NB), ns(nsz);
+    if (kind == RSM_NS_INCLUSION) {
+        for (uint32_t i = 0; i < n_shares; ++i) {
+            const uint8_t* sh = shares + (size_t)i * share_size;
+            if (index < k && start + i < k) memcpy(ns.data(), sh, nsz);  // quadrant 0
+            else memset(ns.data(), 0xFF, nsz);
+            if (memcmp(ns.data(), nid, nsz) != 0) return done(RSM_PROOF_NAMESPACE);
+            uint8_t* o = &cur[(size_t)i * NB];
+            memcpy(o, ns.data(), nsz);
+            memcpy(o + nsz, ns.data(), nsz);
+            Sha256 s;
+            const uint8_t pre = 0x00;
+            s.update(&pre, 1);
+            s.update(ns.data(), nsz);
+            s.update(sh, share_size);
+            s.final(o + 2 * nsz);
+        }
+    } else {
+        const uint8_t* leaf = record + 16 + (size_t)2 * L * NB;
+        if (memcmp(leaf, leaf + nsz, nsz) != 0 || memcmp(leaf, nid, nsz) <= 0) return done(RSM_PROOF_NAMESPACE);
+        memcpy(cur.data(), leaf, NB);
+    }
+    // 3. nothing of nid lies under a proof node
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        const uint8_t* nd = record + 16 + (size_t)i * NB;
+        if (i < n_left ? memcmp(nd + nsz, nid, nsz) >= 0 : memcmp(nd, nid, nsz) <= 0) return done(RSM_PROOF_INCOMPLETE);
+    }
+    // 4, 5. the fold, level by level: the range's nodes a .. last of a level, the proof's
+    // left node in front when a is odd, its right node behind when last is even and not
+    // the level's last node; an unpaired last node is carried up
+    uint32_t a = start, last = end - 1, li = n_left, ri = n_left;  // next left node: li - 1; next right: ri
+    std::vector<uint8_t> row, nxt;
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint32_t cnt = (uint32_t)(((uint64_t)n_leaves + (1ull << l) - 1) >> l);
+        row.clear();
+        if (a & 1u) {
+            const uint8_t* nd = record + 16 + (size_t)(--li) * NB;
+            row.insert(row.end(), nd, nd + NB);
+            --a;
+        }
+        row.insert(row.end(), cur.begin(), cur.end());
+        if (!(last & 1u) && last + 1 < cnt) {
+            const uint8_t* nd = record + 16 + (size_t)(ri++) * NB;
+            row.insert(row.end(), nd, nd + NB);
+            ++last;
+        }
+        const uint32_t have = last - a + 1, np = have / 2;  // a is even; an odd count ends in the carried node
+        nxt.assign((size_t)(np + (have & 1u)) * NB, 0);
+        for (uint32_t j = 0; j < np; ++j) {
+            const uint8_t* lft = &row[(size_t)2 * j * NB];
+            uint8_t* o = &nxt[(size_t)j * NB];
+            if (!nmt_pair(lft, lft + NB, nsz, ig, o)) return done(RSM_PROOF_ORDER);
+            Sha256 s;
+            const uint8_t pre = 0x01;
+            s.update(&pre, 1);
+            s.update(lft, 2 * (size_t)NB);
+            s.final(o + 2 * nsz);
+        }
+        if (have & 1u) memcpy(&nxt[(size_t)np * NB], &row[(size_t)(have - 1) * NB], NB);
+        cur.swap(nxt);
+        a >>= 1;
+        last >>= 1;
+    }
+    return done(memcmp(cur.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT);
 }

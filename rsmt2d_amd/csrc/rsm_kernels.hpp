@@ -214,6 +214,46 @@ hipError_t launch_proof_gather(const uint32_t* d_store, uint32_t W, uint32_t squ
                                const ProofSample* d_samples, uint32_t n, uint8_t* d_records, hipStream_t st);
 hipError_t launch_share_gather(const uint8_t* d_eds, uint32_t W, uint32_t S, const ProofSample* d_samples, uint32_t n,
                                uint8_t* d_shares, hipStream_t st);
+// ---- namespace proofs (DESIGN.md §4 "Namespace proofs"; kernels_nsproof.hip) --------
+// A query: every share of namespace `nid` (8 big-endian words, zero padded, as the
+// store's leaf records hold a namespace) in row / column `index` of square `square`.
+struct NsQuery {
+    uint32_t square, axis, index;
+    uint32_t nid[8];
+};
+constexpr uint32_t kNsEmpty = 0, kNsInclusion = 1, kNsAbsence = 2, kNsTree = 3;
+// The range proof of leaves [start, end) of a tree of W leaves, by levels: with a = start
+// and last = end - 1, level l gives the left node (l, a - 1) when a is odd and the right
+// node (l, last + 1) when last is even and below the level's last node; then both halve.
+// Returns the node count; *n_left: how many of them are left nodes.
+__host__ __device__ constexpr uint32_t ns_range_nodes(uint32_t W, uint32_t start, uint32_t end, uint32_t* n_left) {
+    uint32_t a = start, last = end - 1, nl = 0, nr = 0;
+    for (uint32_t l = 0, L = proof_levels(W); l < L; ++l) {
+        if (a & 1u) ++nl;
+        if (!(last & 1u) && last + 1 < proof_level_count(W, l)) ++nr;
+        a >>= 1;
+        last >>= 1;
+    }
+    *n_left = nl;
+    return nl + nr;
+}
+// Records of 16 + (2L + 1) * (2 ns + 32) bytes (any alignment): u32 kind | start | end |
+// n_nodes, the nodes (left ones top-down, then right ones bottom-up), zeros up to slot
+// 2L, slot 2L the leaf node of an absence proof.  Three steps, all on `st`:
+//   locate : one lane per query -- the tree's status word, its top node, two binary
+//            searches (at most L + 1 probes each) over the vector's level-0 namespaces;
+//            writes the record header and the query's share count into d_offsets[i]
+//   scan   : d_offsets[0 .. n] becomes the exclusive prefix sum of the counts
+//            (d_offsets[n]: the total), one workgroup
+//   gather : one lane per (query, slot) copies or zero-fills its node; one wave per
+//            query copies its shares (16-byte words) to d_shares + d_offsets[i] * S when
+//            d_offsets[i + 1] <= shares_cap (d_shares nullable: no shares)
+// d_status: 2W words per square as launch_nmt_nodes wrote them.  Queries are validated
+// on the host.
+hipError_t launch_ns_proofs(const uint32_t* d_store, const uint32_t* d_status, const uint8_t* d_eds, uint32_t W,
+                            uint32_t S, uint32_t squares, uint32_t ns, const NsQuery* d_queries, uint32_t n,
+                            uint8_t* d_records, uint32_t* d_offsets, uint8_t* d_shares, uint64_t shares_cap,
+                            hipStream_t st);
 // Proof verification (DESIGN.md §4 "Verification"; the DefaultTree kernel in
 // kernels_sha.hip, the NMT kernels in kernels_nmt.hip): one lane per sample hashes its
 // share (d_shares: [n][S], 16-byte aligned), folds the siblings of its record

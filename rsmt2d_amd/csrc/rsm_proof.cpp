@@ -3,7 +3,8 @@
 // rsm_eds_proofs of the ExtendedDataSquare object (device path with a cached node
 // store; host restatements of merkle.cpp otherwise); the receiving side:
 // rsm_proofs_verify_dev over the verify kernels (kernels_sha.hip, kernels_nmt.hip) and
-// rsm_eds_import_samples (verify, then SetCell).  Format: include/rsmt2d_hip.h.
+// rsm_eds_import_samples (verify, then SetCell); namespace proofs: rsm_ns_proofs_dev over
+// kernels_nsproof.hip and rsm_eds_namespace_proofs.  Formats: include/rsmt2d_hip.h.
 #include "eds_internal.hpp"
 
 #include <algorithm>
@@ -13,6 +14,10 @@
 using namespace rsm;
 
 static_assert(sizeof(rsm_sample) == sizeof(ProofSample) && sizeof(rsm_sample) == 16, "rsm_sample is the kernels' sample");
+
+static_assert(sizeof(NsQuery) == 44 && kNsEmpty == RSM_NS_EMPTY && kNsInclusion == RSM_NS_INCLUSION &&
+                  kNsAbsence == RSM_NS_ABSENCE && kNsTree == RSM_NS_TREE,
+              "the kernels' namespace proof kinds are the C ABI's");
 
 static_assert(kProofOk == RSM_PROOF_OK && kProofMalformed == RSM_PROOF_MALFORMED && kProofOrder == RSM_PROOF_ORDER &&
                   kProofRoot == RSM_PROOF_ROOT,
@@ -42,11 +47,11 @@ int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
                 s[i].axis, s[i].index, s[i].pos);
 }
 
-// Uploads n samples through the stream's staging buffers (ss.mu held): *ds is the
-// device copy, valid for kernels enqueued on `st` before the next call on it.
-int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
+// Uploads `bytes` of a call's host arguments through the stream's staging buffers
+// (ss.mu held): *dev is the device copy, valid for kernels enqueued on `st` before the
+// next call on it.
+int stage_bytes(hipStream_t st, StreamScratch& ss, const void* src, size_t bytes, const void** dev) {
     hipError_t e;
-    const size_t bytes = (size_t)n * sizeof(rsm_sample);
     // the staging buffer is free once the previous call's upload has left it; the
     // device copy is read by that call's kernels, ordered before this upload on `st`
     if (ss.samp_ev && (e = hipEventSynchronize(ss.samp_ev)) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
@@ -59,12 +64,68 @@ int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, 
         if ((e = ss.samp_dev.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipMalloc (samples)");
     }
     if ((e = ss.samp_host.ensure(bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc (samples)");
-    memcpy(ss.samp_host.ptr, samples, bytes);
+    memcpy(ss.samp_host.ptr, src, bytes);
     if ((e = hipMemcpyAsync(ss.samp_dev.ptr, ss.samp_host.ptr, bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
         return hip_fail(e, "H2D samples");
     if ((e = hipEventRecord(ss.samp_ev, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    *ds = static_cast<const ProofSample*>(ss.samp_dev.ptr);
+    *dev = ss.samp_dev.ptr;
     return RSM_OK;
+}
+
+int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
+    const void* d = nullptr;
+    if (int rc = stage_bytes(st, ss, samples, (size_t)n * sizeof(rsm_sample), &d)) return rc;
+    *ds = static_cast<const ProofSample*>(d);
+    return RSM_OK;
+}
+
+uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// The NMT params of (tree_fn, user), or nullptr.
+const rsm_nmt_params* nmt_of(rsm_tree_root_fn tree_fn, void* user) {
+    return tree_fn == rsm_nmt_tree_root && user ? static_cast<const rsm_nmt_params*>(user) : nullptr;
+}
+
+// Whether a complete square with a context takes the device path for tree `nmt`.
+bool store_path(rsm_eds* e, const rsm_nmt_params* nmt, DevTree* dt) {
+    const bool complete = memchr(e->present.data(), 0, e->present.size()) == nullptr;
+    return e->ctx && complete && proof_tree_for(e->width, nmt, dt) && rsm_proof_nodes_bytes(e->width, nmt, 1) != 0 &&
+           (!dt->nmt || e->S >= dt->p.namespace_size);
+}
+
+// The square's cached node store for tree `dt`, built once (ctx->eds_mu held, device
+// selected); later calls only gather.
+int ensure_store(rsm_eds* e, const rsm_nmt_params* nmt, const DevTree& dt) {
+    rsm_ctx* ctx = e->ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t W = e->width, S = e->S;
+    hipError_t r;
+    ProofStore& ps = e->proofs;
+    const bool same =
+        ps.d_nodes && ps.ctx == ctx && ps.nmt == dt.nmt && (!dt.nmt || memcmp(&ps.p, &dt.p, sizeof(dt.p)) == 0);
+    if (same) return RSM_OK;
+    ps.drop();
+    DevBuf& sq = ctx->eds.eds;
+    DevBuf& sb = ctx->eds.status;
+    if ((r = sq.ensure(e->data.size())) != hipSuccess || (r = sb.ensure((size_t)2 * W * 4)) != hipSuccess)
+        return hip_fail(r, "hipMalloc (proof square)");
+    if ((r = hipMalloc(&ps.d_nodes, store_bytes(dt, W, 1))) != hipSuccess) {
+        ps.d_nodes = nullptr;
+        return hip_fail(r, "hipMalloc (node store)");
+    }
+    ps.ctx = ctx;
+    ps.nmt = dt.nmt;
+    ps.p = dt.p;
+    ps.status.assign((size_t)2 * W, 0);
+    int rc = RSM_OK;
+    if ((r = hipMemcpyAsync(sq.ptr, e->data.data(), e->data.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
+        rc = hip_fail(r, "H2D square");
+    if (!rc) rc = rsm_proof_nodes_dev(ctx, sq.ptr, W, S, 1, nmt, ps.d_nodes, nullptr, sb.ptr, st);
+    if (!rc && (r = hipMemcpyAsync(ps.status.data(), sb.ptr, (size_t)2 * W * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        rc = hip_fail(r, "D2H tree status");
+    if (!rc && (r = hipStreamSynchronize(st)) != hipSuccess) rc = hip_fail(r, "proof stream");
+    if (rc) ps.drop();
+    return rc;
 }
 
 }  // namespace
@@ -256,9 +317,8 @@ int rsm_eds_import_samples(rsm_eds* e, const uint8_t* row_roots, const uint8_t* 
 int rsm_eds_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_sample* samples, uint32_t n,
                    uint8_t* records_out, uint8_t* shares_out) {
     if (!e || (n && (!samples || !records_out))) return fail(RSM_EINVAL, "rsm_eds_proofs: bad arguments");
-    const rsm_nmt_params* nmt = nullptr;
-    if (tree_fn == rsm_nmt_tree_root && user) nmt = static_cast<const rsm_nmt_params*>(user);
-    else if (tree_fn != nullptr && tree_fn != rsm_default_tree_root)
+    const rsm_nmt_params* nmt = nmt_of(tree_fn, user);
+    if (!nmt && tree_fn != nullptr && tree_fn != rsm_default_tree_root)
         return fail(RSM_EUNSUPPORTED, "rsm_eds_proofs: proofs are built for the DefaultTree and the NMT only");
     const uint32_t W = e->width, S = e->S;
     const uint32_t bad = first_bad_sample(samples, n, 1, W);
@@ -273,43 +333,14 @@ int rsm_eds_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_s
                             samples[i].index);
     if (n == 0) return RSM_OK;
     DevTree dt;
-    const bool complete = memchr(e->present.data(), 0, e->present.size()) == nullptr;
-    if (e->ctx && complete && proof_tree_for(W, nmt, &dt) && rsm_proof_nodes_bytes(W, nmt, 1) != 0 &&
-        (!dt.nmt || S >= dt.p.namespace_size)) {
+    if (store_path(e, nmt, &dt)) {
         rsm_ctx* ctx = e->ctx;
         std::lock_guard<std::mutex> lk(ctx->eds_mu);
         if (int rc = use_device(ctx)) return rc;
         hipStream_t st = ctx->stream;
         hipError_t r;
+        if (int rc = ensure_store(e, nmt, dt)) return rc;
         ProofStore& ps = e->proofs;
-        const bool same = ps.d_nodes && ps.ctx == ctx && ps.nmt == dt.nmt &&
-                          (!dt.nmt || memcmp(&ps.p, &dt.p, sizeof(dt.p)) == 0);
-        if (!same) {  // build the node store once; later calls only gather
-            ps.drop();
-            DevBuf& sq = ctx->eds.eds;
-            DevBuf& sb = ctx->eds.status;
-            if ((r = sq.ensure(e->data.size())) != hipSuccess || (r = sb.ensure((size_t)2 * W * 4)) != hipSuccess)
-                return hip_fail(r, "hipMalloc (proof square)");
-            if ((r = hipMalloc(&ps.d_nodes, store_bytes(dt, W, 1))) != hipSuccess) {
-                ps.d_nodes = nullptr;
-                return hip_fail(r, "hipMalloc (node store)");
-            }
-            ps.ctx = ctx;
-            ps.nmt = dt.nmt;
-            ps.p = dt.p;
-            ps.status.assign((size_t)2 * W, 0);
-            int rc = RSM_OK;
-            if ((r = hipMemcpyAsync(sq.ptr, e->data.data(), e->data.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
-                rc = hip_fail(r, "H2D square");
-            if (!rc) rc = rsm_proof_nodes_dev(ctx, sq.ptr, W, S, 1, nmt, ps.d_nodes, nullptr, sb.ptr, st);
-            if (!rc && (r = hipMemcpyAsync(ps.status.data(), sb.ptr, (size_t)2 * W * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
-                rc = hip_fail(r, "D2H tree status");
-            if (!rc && (r = hipStreamSynchronize(st)) != hipSuccess) rc = hip_fail(r, "proof stream");
-            if (rc) {
-                ps.drop();
-                return rc;
-            }
-        }
         for (uint32_t i = 0; i < n; ++i)
             if (ps.status[(size_t)samples[i].axis * W + samples[i].index])
                 return fail(RSM_ETREE, "tree error proving a share of %s %u (namespace order)",
@@ -335,6 +366,125 @@ int rsm_eds_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_s
     }
     if (shares_out)
         for (uint32_t i = 0; i < n; ++i) memcpy(shares_out + (size_t)i * S, cell_of(samples[i]), S);
+    return RSM_OK;
+}
+
+int rsm_ns_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status, const void* d_eds, uint32_t width,
+                      uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt, const rsm_ns_query* queries,
+                      const uint8_t* nids, uint32_t n, void* d_records, void* d_offsets, void* d_shares,
+                      uint64_t shares_cap, void* stream) {
+    if (!ctx || !d_nodes || !d_status || width == 0 || (n && (!queries || !nids || !d_records || !d_offsets)))
+        return fail(RSM_EINVAL, "rsm_ns_proofs_dev: bad arguments");
+    if (!nmt) return fail(RSM_EUNSUPPORTED, "rsm_ns_proofs_dev: the DefaultTree has no namespaces");
+    if (d_shares && !d_eds) return fail(RSM_EINVAL, "rsm_ns_proofs_dev: d_shares needs d_eds");
+    if (d_shares && ((reinterpret_cast<uintptr_t>(d_shares) & 15u) || (reinterpret_cast<uintptr_t>(d_eds) & 15u)))
+        return fail(RSM_EINVAL, "rsm_ns_proofs_dev: d_eds and d_shares must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_nodes) & 15u) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return fail(RSM_EINVAL, "rsm_ns_proofs_dev: d_nodes must be 16-byte, d_status and d_offsets 4-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    DevTree t;
+    if (!proof_tree_for(width, nmt, &t) || !t.nmt || rsm_proof_nodes_bytes(width, nmt, count ? count : 1) == 0)
+        return fail(RSM_EUNSUPPORTED, "rsm_ns_proofs_dev: %u squares of width %u (NMT) not supported", count, width);
+    if (n > (1u << 20)) return fail(RSM_EINVAL, "rsm_ns_proofs_dev: at most %u queries per call", 1u << 20);
+    if (n == 0 || count == 0) return RSM_OK;
+    const uint32_t ns = t.p.namespace_size;
+    std::vector<NsQuery> q(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (queries[i].square >= count || queries[i].axis > 1 || queries[i].index >= width)
+            return fail(RSM_EINVAL, "rsm_ns_proofs_dev: query %u (square %u, axis %u, index %u) is out of range", i,
+                        queries[i].square, queries[i].axis, queries[i].index);
+        q[i] = NsQuery{queries[i].square, queries[i].axis, queries[i].index, {}};
+        for (uint32_t b = 0; b < ns; ++b)  // big-endian words, zero padded, as the leaf records
+            q[i].nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
+    }
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const void* dq = nullptr;
+    if (int rc = stage_bytes(st, ss, q.data(), (size_t)n * sizeof(NsQuery), &dq)) return rc;
+    const hipError_t e = launch_ns_proofs(static_cast<const uint32_t*>(d_nodes), static_cast<const uint32_t*>(d_status),
+                                          static_cast<const uint8_t*>(d_eds), width, share_size, count, ns,
+                                          static_cast<const NsQuery*>(dq), n, static_cast<uint8_t*>(d_records),
+                                          static_cast<uint32_t*>(d_offsets), static_cast<uint8_t*>(d_shares), shares_cap,
+                                          st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "namespace proof kernel launch");
+}
+
+int rsm_eds_namespace_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, int axis, const uint32_t* indices,
+                             uint32_t n, const uint8_t* nid, uint8_t* records_out, uint32_t* offsets_out,
+                             uint8_t* shares_out, uint64_t shares_cap) {
+    if (!e || !nid || !offsets_out || (axis != RSM_AXIS_ROW && axis != RSM_AXIS_COL) || (n && (!indices || !records_out)))
+        return fail(RSM_EINVAL, "rsm_eds_namespace_proofs: bad arguments");
+    const rsm_nmt_params* nmt = nmt_of(tree_fn, user);
+    if (!nmt) return fail(RSM_EUNSUPPORTED, "rsm_eds_namespace_proofs: namespace proofs are built for the NMT only");
+    const uint32_t W = e->width, S = e->S;
+    const uint32_t RB = rsm_ns_record_bytes(W, nmt);
+    if (RB == 0 || nmt->square_size == 0) return fail(RSM_EINVAL, "rsm_eds_namespace_proofs: namespace size or square size 0");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (indices[i] >= W)
+            return fail(RSM_EINVAL, "rsm_eds_namespace_proofs: %s %u is out of range", axis == 0 ? "row" : "column", indices[i]);
+        for (uint32_t p = 0; p < W; ++p)
+            if (!e->has(e->rr(axis, indices[i], p), e->cc(axis, indices[i], p)))
+                return fail(RSM_ETREE, "can not prove a namespace of incomplete %s %u", axis == 0 ? "row" : "column", indices[i]);
+    }
+    offsets_out[0] = 0;
+    if (n == 0) return RSM_OK;
+    DevTree dt;
+    if (n <= (1u << 20) && store_path(e, nmt, &dt)) {
+        rsm_ctx* ctx = e->ctx;
+        std::lock_guard<std::mutex> lk(ctx->eds_mu);
+        if (int rc = use_device(ctx)) return rc;
+        hipStream_t st = ctx->stream;
+        hipError_t r;
+        if (int rc = ensure_store(e, nmt, dt)) return rc;
+        ProofStore& ps = e->proofs;
+        for (uint32_t i = 0; i < n; ++i)
+            if (ps.status[(size_t)axis * W + indices[i]])
+                return fail(RSM_ETREE, "tree error proving a namespace of %s %u (namespace order)", axis == 0 ? "row" : "column",
+                            indices[i]);
+        // offsets | records in one scratch buffer; the shares are this square's host bytes
+        const size_t o_rec = (size_t)(n + 1) * 4, total = o_rec + (size_t)n * RB;
+        DevBuf& rb = ctx->eds.scratch;
+        DevBuf& sb = ctx->eds.status;
+        if ((r = rb.ensure(total)) != hipSuccess || (r = sb.ensure((size_t)2 * W * 4)) != hipSuccess)
+            return hip_fail(r, "hipMalloc (namespace proof records)");
+        if ((r = hipMemcpyAsync(sb.ptr, ps.status.data(), (size_t)2 * W * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return hip_fail(r, "H2D tree status");
+        std::vector<rsm_ns_query> q(n);
+        std::vector<uint8_t> nids((size_t)n * nmt->namespace_size);
+        for (uint32_t i = 0; i < n; ++i) {
+            q[i] = rsm_ns_query{0, (uint32_t)axis, indices[i]};
+            memcpy(&nids[(size_t)i * nmt->namespace_size], nid, nmt->namespace_size);
+        }
+        auto* d = static_cast<uint8_t*>(rb.ptr);
+        if (int rc = rsm_ns_proofs_dev(ctx, ps.d_nodes, sb.ptr, nullptr, W, S, 1, nmt, q.data(), nids.data(), n, d + o_rec, d,
+                                       nullptr, 0, st))
+            return rc;
+        if ((r = hipMemcpyAsync(offsets_out, d, o_rec, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (r = hipMemcpyAsync(records_out, d + o_rec, (size_t)n * RB, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(r, "D2H namespace proof records");
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(r, "proof stream");
+    } else {
+        std::vector<const uint8_t*> leaves(W);
+        for (uint32_t i = 0; i < n; ++i) {
+            for (uint32_t p = 0; p < W; ++p) leaves[p] = e->cell(e->rr(axis, indices[i], p), e->cc(axis, indices[i], p));
+            uint8_t* rec = records_out + (size_t)i * RB;
+            const int rc = rsm_nmt_namespace_prove(nmt, indices[i], leaves.data(), W, S, nid, rec, nullptr);
+            if (rc == RSM_ETREE)
+                return fail(RSM_ETREE, "tree error proving a namespace of %s %u", axis == 0 ? "row" : "column", indices[i]);
+            if (rc) return fail(rc, "rsm_eds_namespace_proofs: bad tree parameters");
+            offsets_out[i + 1] = offsets_out[i] + (le32(rec) == RSM_NS_INCLUSION ? le32(rec + 8) - le32(rec + 4) : 0u);
+        }
+    }
+    if (shares_out)
+        for (uint32_t i = 0; i < n; ++i) {
+            if (offsets_out[i + 1] == offsets_out[i] || offsets_out[i + 1] > shares_cap) continue;
+            const uint32_t start = le32(records_out + (size_t)i * RB + 4);
+            for (uint32_t p = 0; p < offsets_out[i + 1] - offsets_out[i]; ++p)
+                memcpy(shares_out + (size_t)(offsets_out[i] + p) * S, e->cell(e->rr(axis, indices[i], start + p), e->cc(axis, indices[i], start + p)), S);
+        }
     return RSM_OK;
 }
 

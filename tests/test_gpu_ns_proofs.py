@@ -1,0 +1,242 @@
+"""GPU: namespace proofs out of the device node store (rsm_ns_proofs_dev,
+kernels_nsproof.hip) and the device path of rsm_eds_namespace_proofs.  Records, offsets
+and packed shares are byte-equal to the host restatement (rsm_nmt_namespace_prove) and
+to the recursive helper of tests/ns_proofs.py; every operand the call writes sits
+between guard bands that must come back intact."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import nmt_layouts as NL
+import ns_proofs as H
+import rsmt2d_amd as R
+from oracle import nmt
+
+pytestmark = pytest.mark.gpu
+COUNT = 3
+GUARD = 4096
+
+
+class Guarded:
+    """front guard | operand | back guard in one DeviceBuffer; the operand starts `skew`
+    bytes past a 64-byte boundary and is filled with a pattern of its own."""
+
+    def __init__(self, nbytes, skew, seed):
+        g = np.random.default_rng([0x4E53, seed, nbytes])
+        self.front, self.n = GUARD + skew, nbytes
+        self.sent = g.integers(0, 256, self.front + nbytes + GUARD, dtype=np.uint8)
+        self.buf = R.DeviceBuffer(len(self.sent))
+        self.buf.upload(self.sent)
+        self.ptr = self.buf.ptr + self.front
+
+    def result(self):
+        got = self.buf.download()
+        assert np.array_equal(got[:self.front], self.sent[:self.front]), "a store landed before the operand"
+        assert np.array_equal(got[self.front + self.n:], self.sent[self.front + self.n:]), \
+            "a store landed past the operand"
+        return got[self.front:self.front + self.n]
+
+    def untouched(self, lo, hi):
+        """The pattern the operand's bytes [lo, hi) were sent with."""
+        return self.sent[self.front + lo:self.front + hi]
+
+    def free(self):
+        self.buf.free()
+
+
+def device_proofs(lib, batch, k, ns, ig, S, queries, nids, cap=None, total=None):
+    """One node-store build and one rsm_ns_proofs_dev over `batch` ([count][W][W][S]):
+    (records, offsets, the shares operand, its Guarded pattern accessor, statuses)."""
+    ctx = R.device_context(0)
+    count, W = batch.shape[0], batch.shape[1]
+    p = R.NmtParams(ns, int(ig), k)
+    pp = ctypes.byref(p)
+    n, rb = len(queries), H.record_bytes(W, ns)
+    cap = total if cap is None else cap
+    d = R.DeviceBuffer(batch.size)
+    nodes = R.DeviceBuffer(int(lib.rsm_proof_nodes_bytes(W, pp, count)))
+    status = R.DeviceBuffer(count * 2 * W * 4)
+    recs, offs, shs = Guarded(n * rb, 3, 1), Guarded((n + 1) * 4, 4, 2), Guarded(max(cap, 1) * S, 0, 3)
+    try:
+        d.upload(batch.reshape(-1))
+        arr = (R.NsQuery * n)(*[R.NsQuery(*q) for q in queries])
+        R._check(lib.rsm_proof_nodes_dev(ctx, d.ptr, W, S, count, pp, nodes.ptr, None, status.ptr, None))
+        R._check(lib.rsm_ns_proofs_dev(ctx, nodes.ptr, status.ptr, d.ptr, W, S, count, pp, arr, b"".join(nids), n,
+                                       recs.ptr, offs.ptr, shs.ptr, cap, None))
+        R._check(lib.rsm_sync(ctx))
+        st = status.download(count * 2 * W * 4).view(np.uint32).copy()
+        return recs.result().tobytes(), offs.result().view(np.uint32).copy(), shs.result().copy(), shs, st
+    finally:
+        for b in (d, nodes, status, recs, offs, shs):
+            b.free()
+
+
+def c_prove(lib, p, index, shares, nid):
+    keep, ptrs, _ = R._bufs(shares)
+    rec = ctypes.create_string_buffer(H.record_bytes(len(shares), p.namespace_size))
+    rc = lib.rsm_nmt_namespace_prove(ctypes.byref(p), index, ptrs, len(shares), len(shares[0]), nid, rec, None)
+    return rc, rec.raw
+
+
+def expect(lib, batch, k, ns, ig, vectors):
+    """Queries over `vectors` of every square with what the helper says of each:
+    (queries, nids, records, share lists); a failing tree is asked for its first leaf's
+    namespace and owes kind 3."""
+    W = batch.shape[1]
+    p = R.NmtParams(ns, int(ig), k)
+    queries, nids, records, shares = [], [], [], []
+    for s in range(batch.shape[0]):
+        for axis, index in vectors:
+            leaves = H.vector_shares(batch[s], axis, index)
+            try:
+                tree = H.Tree(leaves, index, k, ns, ig)
+            except nmt.NmtError:
+                tree = None
+            asked = H.query_namespaces(tree.names, ns) if tree else [leaves[0][:ns], b"\xff" * ns]
+            for nid in asked:
+                queries.append((s, axis, index))
+                nids.append(nid)
+                rc, host = c_prove(lib, p, index, leaves, nid)
+                if tree is None:
+                    assert rc == R.RSM_ETREE
+                    records.append(H.record_of(W, ns, H.TREE, 0, 0, [], None))
+                    shares.append([])
+                    continue
+                want = H.prove_namespace(tree, nid)
+                records.append(H.record_of(W, ns, *want))
+                assert rc == 0 and host == records[-1], (s, axis, index, nid.hex())
+                shares.append(leaves[want[1]:want[2]] if want[0] == H.INCLUSION else [])
+    return queries, nids, records, shares
+
+
+def check(lib, batch, k, ns, ig, S, vectors):
+    queries, nids, records, shares = expect(lib, batch, k, ns, ig, vectors)
+    total = sum(len(x) for x in shares)
+    rec, offs, sh, _, _ = device_proofs(lib, batch, k, ns, ig, S, queries, nids, total=total)
+    rb = H.record_bytes(batch.shape[1], ns)
+    assert list(offs) == list(np.cumsum([0] + [len(x) for x in shares]))
+    for i, want in enumerate(records):
+        assert rec[i * rb:(i + 1) * rb] == want, (queries[i], nids[i].hex(), rec[i * rb:i * rb + 16].hex())
+    assert sh[:total * S].tobytes() == b"".join(b"".join(x) for x in shares)
+    return queries, nids, records, shares
+
+
+@pytest.mark.parametrize("ig", [True, False])
+@pytest.mark.parametrize("ns", [1, 8, 29])
+@pytest.mark.parametrize("k", [1, 2, 3, 6, 8])
+def test_device_records_offsets_shares(lib, k, ns, ig):
+    """Every layout, three squares to a batch; W = 6 and 12 carry nodes up."""
+    layouts = NL.all_layouts(ns)
+    kinds = set()
+    for b in range(0, len(layouts), COUNT):
+        names = (layouts[b:b + COUNT] * COUNT)[:COUNT]
+        batch = np.stack([NL.square(k, ns, 64, name, 7) for name in names])
+        _, _, records, _ = check(lib, batch, k, ns, ig, 64, H.vectors(k))
+        kinds |= {int.from_bytes(r[:4], "little") for r in records}
+    assert kinds == ({H.EMPTY, H.INCLUSION, H.ABSENCE} if k >= 2 else kinds)
+
+
+def test_k32_runs(lib):
+    k, ns, S = 32, 29, 512
+    batch = np.stack([NL.square(k, ns, S, "runs", seed) for seed in range(COUNT)])
+    _, _, records, shares = check(lib, batch, k, ns, True, S, H.vectors(k))
+    assert max(len(x) for x in shares) > 1 and {int.from_bytes(r[:4], "little") for r in records} == {0, 1, 2}
+
+
+def test_failing_trees(lib):
+    """invert makes trees fail: kind 3, no nodes, no shares; their neighbours are served."""
+    k, ns = 6, 8
+    good = NL.square(k, ns, 64, "ladder:7", 9)
+    batch = np.stack([NL.invert(good, (1, 0), (1, 4), ns), good, NL.invert(good, 0, 3, ns)])
+    vectors = [(a, i) for a in (0, 1) for i in range(2 * k)]
+    queries, nids, records, _ = check(lib, batch, k, ns, True, 64, vectors)
+    kinds = [int.from_bytes(r[:4], "little") for r in records]
+    assert H.TREE in kinds and H.INCLUSION in kinds
+    _, _, _, _, st = device_proofs(lib, batch, k, ns, True, 64, queries, nids, total=0, cap=0)
+    for (s, a, i), kind in zip(queries, kinds):
+        assert (kind == H.TREE) == bool(st[s * 4 * k + a * 2 * k + i])
+
+
+def test_shares_cap(lib):
+    """A capacity below the total: offsets and the total are complete, exactly the queries
+    that end at or below the capacity are written, every other byte keeps its pattern."""
+    k, ns, S = 6, 8, 64
+    batch = np.stack([NL.square(k, ns, S, name, 5) for name in ("single", "runs", "max_tail")])
+    queries, nids, records, shares = expect(lib, batch, k, ns, False, H.vectors(k))
+    lens = [len(x) for x in shares]
+    ends = np.cumsum(lens)
+    total = int(ends[-1])
+    rb = H.record_bytes(2 * k, ns)
+    for cap in (0, 1, total // 3, total - 1):
+        rec, offs, sh, guard, _ = device_proofs(lib, batch, k, ns, False, S, queries, nids, cap=cap)
+        assert list(offs) == [0] + list(ends) and rec == b"".join(records)
+        want = guard.untouched(0, max(cap, 1) * S).copy()
+        for i, x in enumerate(shares):
+            if x and ends[i] <= cap:
+                want[(ends[i] - lens[i]) * S:ends[i] * S] = np.frombuffer(b"".join(x), np.uint8)
+        assert np.array_equal(sh, want), cap
+        assert len(rec) == len(queries) * rb
+
+
+def test_arguments(lib):
+    ctx = R.device_context(0)
+    p = R.NmtParams(8, 1, 2)
+    pp = ctypes.byref(p)
+    buf = R.DeviceBuffer(1 << 16)
+    q = (R.NsQuery * 1)(R.NsQuery(0, 0, 0))
+    try:
+        call = lambda nmt, query, n, count=1: lib.rsm_ns_proofs_dev(ctx, buf.ptr, buf.ptr, buf.ptr, 4, 64, count, nmt, query,
+                                                                    bytes(8), n, buf.ptr, buf.ptr, buf.ptr, 4, None)
+        assert call(None, q, 1) == R.RSM_EUNSUPPORTED
+        assert call(pp, (R.NsQuery * 1)(R.NsQuery(1, 0, 0)), 1) == R.RSM_EINVAL
+        assert call(pp, (R.NsQuery * 1)(R.NsQuery(0, 2, 0)), 1) == R.RSM_EINVAL
+        assert call(pp, (R.NsQuery * 1)(R.NsQuery(0, 0, 4)), 1) == R.RSM_EINVAL
+        assert call(pp, q, (1 << 20) + 1) == R.RSM_EINVAL
+        assert call(pp, q, 0) == 0 and call(pp, q, 1, count=0) == 0  # nothing launched
+        wide = R.NmtParams(8, 1, 1024)
+        assert lib.rsm_ns_proofs_dev(ctx, buf.ptr, buf.ptr, buf.ptr, 2048, 64, 1, ctypes.byref(wide), q, bytes(8), 1,
+                                     buf.ptr, buf.ptr, None, 0, None) == R.RSM_EUNSUPPORTED
+    finally:
+        buf.free()
+
+
+def _ods(k, ns, S, layout, seed):
+    rng = np.random.default_rng([seed, k, ns])
+    ods = rng.integers(0, 256, (k, k, S), dtype=np.uint8)
+    ods[:, :, :ns] = NL.namespaces(k, ns, layout, rng).reshape(k, k, ns)
+    return ods
+
+
+@pytest.mark.parametrize("k,layout", [(8, "runs"), (3, "near_max"), (6, "max_tail")])
+def test_namespace_data_device_and_host_squares(lib, k, layout):
+    """NamespaceData of a device-backed square equals that of a context-free one, and each
+    proof verifies against RowRoots(); prove_namespaces_dev gives the same proofs."""
+    ns, S, W = 29, 64, 2 * k
+    ods = _ods(k, ns, S, layout, 21)
+    ctor = R.newErasuredNamespacedMerkleTreeConstructor(k, ns)
+    eds = R.ComputeExtendedDataSquare([ods[r, c].tobytes() for r in range(k) for c in range(k)], R.NewLeoRSCodec(), ctor)
+    flat = eds.Flattened()
+    host = R.ImportExtendedDataSquare(flat, R.NewLeoRSCodec(), ctor)
+    roots = eds.RowRoots()
+    names = sorted({ods[r, c, :ns].tobytes() for r in range(k) for c in range(k)})
+    as_tuple = lambda pr: (pr.kind, pr.start, pr.end, pr.nodes, pr.leaf_node, pr.shares)
+    buf = R.DeviceBuffer(W * W * S)
+    try:
+        buf.upload(np.frombuffer(b"".join(flat), np.uint8))
+        for nid in names[:6] + names[-2:] + [bytes(ns), b"\xff" * ns, H._add(names[0], 1)]:
+            dev, ref = eds.NamespaceData(nid), host.NamespaceData(nid)
+            assert [(r, as_tuple(pr)) for r, pr in dev] == [(r, as_tuple(pr)) for r, pr in ref]
+            for r, pr in dev:
+                assert pr.verify(roots[r], nid) == H.OK
+                if pr.kind == H.INCLUSION:
+                    assert pr.shares == flat[r * W + pr.start:r * W + pr.end]
+            if nid in names and nid != b"\xff" * ns:  # (0xFF.. is also every parity leaf's)
+                assert sum(len(pr.shares) for _, pr in dev) == sum(ods[r, c, :ns].tobytes() == nid
+                                                                   for r in range(k) for c in range(k))
+            cols = eds.NamespaceProofs(nid, R.Col)
+            assert [as_tuple(pr) for pr in cols] == [as_tuple(pr) for pr in host.NamespaceProofs(nid, R.Col)]
+            direct = R.prove_namespaces_dev(buf, W, S, [(0, R.Col, c) for c in range(W)], [nid] * W, ctor.params)
+            assert [as_tuple(pr) for pr in direct] == [as_tuple(pr) for pr in cols]
+    finally:
+        buf.free()
