@@ -21,6 +21,12 @@ extern "C" {
  * exchange stores (the round-5 body), 58001 = 32-bit stores + the tail of the large
  * layers inside the exchange reads, 58002 = production (64-bit stores), 58003 = 64-bit
  * stores + the tail inside the reads; 58030..58033 = the same with the phase timeline.
+ * Top of the set of the same kernel (correct output): 59000 = the round-7 body (h1 copied
+ * out of its landing registers, the next set's h1 loads at the top), 59001 / 59002 = h1's
+ * first transpose stage reading the landing registers (fixed lane offsets / general form),
+ * 59003 / 59005 = production (copies, the loads after the small IFFT of h0), 59004 / 59006 =
+ * both changes, 59007 = 59000 in the general form; 59030 / 59031 / 59033 / 59034 = 59000 /
+ * 59001 / 59003 / 59004 with the phase timeline.
  * rev_col: column pass in reverse set order; xcd: bit 0 rows / bit 1 columns in
  * XCD-grouped set order. */
 int rsm_diag_set_bs_mode(int mode, int rev_col, int xcd);

@@ -253,8 +253,13 @@ static void emit_xch(int G) {
 // The inverse runs the steps backwards (same count), so planes -> bytes restores the
 // exact byte order the stores need.
 static const int kTpFix[8] = {1, 0, 0, 31, 0, 31, 29, 28};     // rotl per plane after the stages
+// Forward only, for a wave whose bytes land in registers other than the ones the planes
+// live in (bs_split_wave: h1 lands in P, its planes in X[8..15]): a stage's two selects
+// may write any destination, so the FIRST stage (t = 2) can read `src` and write w -- the
+// move costs no instruction.  si0 / si1: the stages [si0, si1) in running order (forward:
+// stage si is t = 2 - si); fix: the fix-up rotations.  src == nullptr: in place.
 static void tp_ops(bool inverse, const int (&w)[8], int tmp0, int tmp1, int mF0, int mCC, int mAA,
-                   std::vector<std::string>& out) {
+                   std::vector<std::string>& out, const int* src = nullptr, int si0 = 0, int si1 = 3, bool fix = true) {
     static const int pairs[3][4][2] = {{{0, 1}, {2, 3}, {4, 5}, {6, 7}},
                                        {{0, 2}, {1, 3}, {4, 6}, {5, 7}},
                                        {{0, 4}, {1, 5}, {2, 6}, {3, 7}}};
@@ -269,22 +274,25 @@ static void tp_ops(bool inverse, const int (&w)[8], int tmp0, int tmp1, int mF0,
         snprintf(b, sizeof b, "v_bitop3_b32 %%%d, %%%d, %%%d, %%%d bitop3:0xd8", d, y, x, m);
         out.push_back(b);
     };
-    if (inverse)
+    if (inverse && fix)
         for (int p = 0; p < 8; ++p)
             if (kTpFix[p]) rot(w[p], w[p], kTpFix[p]);
-    for (int si = 0; si < 3; ++si) {
+    for (int si = si0; si < si1; ++si) {
         const int t = inverse ? si : 2 - si, s = 1 << t, M = mask[t];
         for (int q = 0; q < 4; q += 2) {  // two swaps interleaved (independent instructions)
             int tmp[2] = {tmp0, tmp1};
             std::vector<std::string> st[2];
             for (int h = 0; h < 2; ++h) {
                 const int a = w[pairs[t][q + h][0]], bb = w[pairs[t][q + h][1]], r = tmp[h];
+                // the stage's inputs (forward, first stage of a from-`src` block: the landing registers)
+                const bool from = src && !inverse && si == si0;
+                const int ia = from ? src[pairs[t][q + h][0]] : a, ib = from ? src[pairs[t][q + h][1]] : bb;
                 const bool cb = cfg[t][q + h] == 'b';
                 std::vector<std::string> o;
                 std::swap(o, out);
                 if (!inverse) {
-                    if (cb) { rot(r, bb, 32 - s); sel(bb, M, a, r); sel(a, M, r, a); }
-                    else { rot(r, a, s); sel(a, M, r, bb); sel(bb, M, bb, r); }
+                    if (cb) { rot(r, ib, 32 - s); sel(bb, M, ia, r); sel(a, M, r, ia); }
+                    else { rot(r, ia, s); sel(a, M, r, ib); sel(bb, M, ib, r); }
                 } else {
                     if (cb) { sel(r, M, a, bb); sel(a, M, bb, a); rot(bb, r, s); }
                     else { sel(r, M, a, bb); sel(bb, M, bb, a); rot(a, r, 32 - s); }
@@ -295,7 +303,7 @@ static void tp_ops(bool inverse, const int (&w)[8], int tmp0, int tmp1, int mF0,
             for (int i = 0; i < 3; ++i) out.push_back(st[0][i]), out.push_back(st[1][i]);
         }
     }
-    if (!inverse)
+    if (!inverse && fix)
         for (int p = 0; p < 8; ++p)
             if (kTpFix[p]) rot(w[p], w[p], 32 - kTpFix[p]);
 }
@@ -310,6 +318,33 @@ static void emit_tp(const char* name, bool inverse) {
     printf("        : \"+v\"(w[0]), \"+v\"(w[1]), \"+v\"(w[2]), \"+v\"(w[3]), \"+v\"(w[4]), \"+v\"(w[5]), \"+v\"(w[6]), "
            "\"+v\"(w[7]),\n          \"=&v\"(t0), \"=&v\"(t1)\n"
            "        : \"s\"(0xF0F0F0F0u), \"s\"(0xCCCCCCCCu), \"s\"(0xAAAAAAAAu));\n}\n");
+}
+
+// First stage (t = 2) of the forward transposes of h1, read from the landing registers
+// P and written to X[8..15] (bs_split_wave, top of the set): the stage's instructions
+// with new destinations, so h1 needs no P -> X copies.  P is dead after the block, as it
+// is after the copies, so the next set's h1 loads may be issued anywhere behind it; the
+// remaining stages and the fix-ups run in the store window of the first exchange
+// (emit_phase_x, from_p).  Diagnostic build only: no gain measured.
+// Operands: %0..%63 = X[8 + j][i] (operand 8j + i, early-clobber outputs), %64 %65
+// temporaries, %66 the mask 0xF0F0F0F0 (SGPR), %67..%130 = P[j][i] (operand 67 + 8j + i,
+// inputs only: the quads P[j][0..3] / P[j][4..7] a dwordx4 load fills stay where they are).
+static void emit_tp1_from_p(const char* name) {
+    std::vector<std::string> ops;
+    for (int j = 0; j < 8; ++j) {
+        int w[8], src[8];
+        for (int i = 0; i < 8; ++i) w[i] = 8 * j + i, src[i] = 67 + 8 * j + i;
+        tp_ops(false, w, 64, 65, 66, -1, -1, ops, src, 0, 1, false);
+    }
+    printf("RSM_BS8_DEV void %s(uint32_t (&X)[16][8], const uint32_t (&P)[8][8]) {\n    uint32_t t0, t1;\n    asm volatile(\n", name);
+    for (size_t i = 0; i < ops.size(); ++i) printf("        \"%s%s\"\n", ops[i].c_str(), i + 1 < ops.size() ? "\\n\\t" : "");
+    printf("        :");
+    for (int j = 0; j < 8; ++j)
+        for (int i = 0; i < 8; ++i) printf(" \"=&v\"(X[%d][%d]),", 8 + j, i);
+    printf(" \"=&v\"(t0), \"=&v\"(t1)\n        : \"s\"(0xF0F0F0F0u)");
+    for (int j = 0; j < 8; ++j)
+        for (int i = 0; i < 8; ++i) printf(", \"v\"(P[%d][%d])", j, i);
+    printf(");\n}\n");
 }
 
 // Interleaved phases of the half-split schedule: the 64 exchange writes of half W
@@ -486,13 +521,15 @@ static void print_spread(const std::vector<std::string>& valu, const std::vector
 // Exchange writes of half W (b64: 32 ds_write_b64, else 64 ds_write_b32) spread through
 // VALU work on half V = 1 - W: kind 0 / 3 the transposes (as emit_phase), kind 1 / 2
 // the large IFFT / FFT of half V (part 0: all of it, 1: without the tail of large_ir).
-static void emit_phase_x(const char* name, int W, int kind, int part, bool b64) {
+// from_p (kind 0): the forward transposes without their first stage, which
+// emit_tp1_from_p has run (stages t = 1, 0 and the fix-ups; the mask 0xF0.. is not passed).
+static void emit_phase_x(const char* name, int W, int kind, int part, bool b64, bool from_p = false) {
     const int V = 1 - W;
     std::vector<std::string> valu, wr;
     std::vector<IrOp> ir;
     if (kind == 1 || kind == 2) ir = large_ir(kind, V, part);
     const int nt = (kind == 0 || kind == 3) ? 2 : std::max(1, ir_temps(ir));
-    const int nm = (kind == 0 || kind == 3) ? 3 : 0;
+    const int nm = from_p ? 2 : (kind == 0 || kind == 3) ? 3 : 0;
     const int mk = 64 + nt, d0 = mk + nm, nd = b64 ? 32 : 64;
     const int va = d0 + nd, vb = va + 1;
     char b[96];
@@ -512,7 +549,8 @@ static void emit_phase_x(const char* name, int W, int kind, int part, bool b64) 
     if (kind == 0 || kind == 3) {
         for (int j = 0; j < 8; ++j) {
             const int w[8] = {8 * j, 8 * j + 1, 8 * j + 2, 8 * j + 3, 8 * j + 4, 8 * j + 5, 8 * j + 6, 8 * j + 7};
-            tp_ops(kind == 3, w, 64, 65, mk, mk + 1, mk + 2, valu);
+            if (from_p) tp_ops(false, w, 64, 65, -1, mk, mk + 1, valu, nullptr, 1, 3, true);
+            else tp_ops(kind == 3, w, 64, 65, mk, mk + 1, mk + 2, valu);
         }
     } else {
         ir_emit(ir, [V](int sym, int i) { return 8 * (sym - 8 * V) + i; }, 64, valu);
@@ -531,6 +569,7 @@ static void emit_phase_x(const char* name, int W, int kind, int part, bool b64) 
     print_temps_ops(nt);
     printf("\n        : ");
     if (nm == 3) printf("\"s\"(0xF0F0F0F0u), \"s\"(0xCCCCCCCCu), \"s\"(0xAAAAAAAAu), ");
+    else if (nm == 2) printf("\"s\"(0xCCCCCCCCu), \"s\"(0xAAAAAAAAu), ");
     for (int v = 0; v < 8; ++v)
         for (int q = 0; q < nd / 8; ++q) {
             if (b64) printf("\"v\"(T[%d][%d]), ", v, q);
@@ -596,6 +635,10 @@ int main(int argc, char** argv) {
     emit_phase("ph_w1_lifft0", 1, 1);
     emit_phase("ph_w0_lfft1", 0, 2);
     emit_phase("ph_w1_tr0", 1, 3);
+    // h1's first transpose stage straight from its landing registers, and the first store
+    // window without that stage (no gain in its A/B: DESIGN.md section 8, round 8)
+    emit_tp1_from_p("tp1_h1_from_p");
+    emit_phase_x("ph_w0_tr1s_w64", 0, 0, 0, true, true);
     printf("#endif\n");
     emit_lmid("lmid_all");
     emit_tp("tp_fwd_dev", false);

@@ -1022,8 +1022,9 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
     // 262144: no LDS-DMA -- h1 of the next set by direct loads into Q right after this
     // set's h0 stores (the LDS region R then holds only exchanges)
     constexpr bool NODMA = (MODE & 262144) != 0 && !LATE0;
-    // production: no LDS-DMA -- P holds h1 of the next set (loaded at the top), h0 of
-    // the next set is loaded into X[0..7] right after this set's h0 stores;
+    // production: no LDS-DMA -- P holds h1 of the next set (loaded after the small IFFT
+    // of h0, LATEP below), h0 of the next set is loaded into X[0..7] right after this
+    // set's h0 stores;
     // 1048576: the LDS-DMA form (h1 of the next set lands in R, A/B)
     constexpr bool XLOAD = (MODE & 1048576) == 0 && !NODMA && !LATE0;
     // 524288: phase timeline into p.trace (diagnostic build)
@@ -1044,6 +1045,23 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
 #ifdef RSM_DIAG
     constexpr bool TAIL = (MODE & 268435456) != 0, W64 = (MODE & 536870912) == 0 && !OLDTP;
 #endif
+    // 1073741824 (kSplitFromP, diagnostic build only): h1's bytes are not copied from
+    // their landing registers P into X[8..15]; the first stage of h1's forward transposes
+    // reads P and writes X (tp1_h1_from_p, at the top of the set, so P is dead where it
+    // was before), and the first store window runs the other two stages and the fix-ups
+    // (ph_w0_tr1s_w64).  The production body's instructions minus the 64 copies; measured:
+    // no gain.
+#ifdef RSM_DIAG
+    constexpr bool FROMP = (MODE & 1073741824) != 0 && XLOAD && IL && !OLDTP && W64;
+#endif
+    // Production: the next set's h1 loads into P are issued after T0 and the small IFFT
+    // of h0; 2097152 (kSplitTopP): at the top of the set (the body up to round 7, A/B).
+    // The compiler's own waits in front of T0 count memory operations in issue order and
+    // must assume the fewest younger ones any path leaves (no stores, no loads at the
+    // top): vmcnt(13) .. vmcnt(0).  With P's 16 loads issued at the top those waits also
+    // cover the first 3 .. all 16 of them, so T0 waited a full load latency for registers
+    // it does not read.
+    constexpr bool LATEP = (MODE & 2097152) == 0 && XLOAD && IL;
     auto tp_fwd = [](uint32_t (&w)[8]) {
         if constexpr (OLDTP) bs8::transpose8_dev(w);
         else bs8::tp_fwd_dev(w);
@@ -1153,7 +1171,11 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
         for (;;) {
             stamp(0);
             // ---- top: h0 from P (XLOAD: h1 from P, h0 already in X); the next item;
-            // its P loads ----
+            // its P loads (LATEP: after the small IFFT of h0) ----
+#ifdef RSM_DIAG
+            if constexpr (FROMP) bs8::tp1_h1_from_p(X, P);
+            else
+#endif
             bs8::sfor<8>([&](auto J) {
                 constexpr int j = decltype(J)::value;
                 bs8::sfor<8>([&](auto I) { X[(XLOAD ? 8 : 0) + j][decltype(I)::value] = P[j][decltype(I)::value]; });
@@ -1168,7 +1190,7 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
             if (pre) {
                 q_item(p, nxt, nsq, nrow, nset);
                 an = addr(nrow, nset);
-                issue_direct(nrow, nxt & kQ1, an);
+                if constexpr (!LATEP) issue_direct(nrow, nxt & kQ1, an);
             }
             // no claim in a workgroup's last set (nothing would take the item)
             if (t0) cand = more ? q_claim(p, qc) : kNone;
@@ -1176,6 +1198,8 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
                 bs8::sfor<8>([&](auto J) { tp_fwd(X[decltype(J)::value]); });
                 bs8::small_ifft_h0_all(X, A);
             }
+            if constexpr (LATEP)
+                if (pre) issue_direct(nrow, nxt & kQ1, an);
             if constexpr (XLOAD) {
             } else if constexpr (NODMA) {
                 bs8::sfor<8>([&](auto J) {
@@ -1214,6 +1238,7 @@ __device__ __forceinline__ void bs_split_wave(const QueuePlan& p_in, uint32_t* l
 #ifdef RSM_DIAG
                 if constexpr (OLDTP) bs8::ph_w0_tr1_old(X, xw, xw + 65536u);
                 else if constexpr (!W64) bs8::ph_w0_tr1(X, xw, xw + 65536u);
+                else if constexpr (FROMP) bs8::ph_w0_tr1s_w64(X, xw, xw + 65536u);  // the first stage ran at the top
                 else
 #endif
                 bs8::ph_w0_tr1_w64(X, xw, xw + 65536u);
@@ -1694,6 +1719,10 @@ bool bs128_queue_applicable(const CodewordSet& rows, const CodewordSet& cols) {
 // default policy +3 % (the Infinity-Cache re-read of Q0 needs the default policy, the
 // last read of Q1 is best non-temporal).
 #ifdef RSM_DIAG
+// bs_split_wave's MODE bits for h1's first transpose stage read from its landing registers
+// and for the next set's h1 loads issued at the top of the set (the round-7 body)
+constexpr int kSplitFromP = 1073741824;
+constexpr int kSplitTopP = 2097152;
 static std::atomic<uint32_t*> g_diag_trace{nullptr};
 void set_bs128_diag_trace(uint32_t* d) { g_diag_trace.store(d); }
 #endif
@@ -1750,6 +1779,25 @@ hipError_t launch_extend_gf8_bs128_queue(const QueuePlan& p0, hipStream_t st) {
         case 58031: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | 536870912 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
         case 58032: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288>), dim3(grid), dim3(512), 0, st, p); break;
         case 58033: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | 268435456>), dim3(grid), dim3(512), 0, st, p); break;
+        // Top of the set A/B (GEO form unless noted): 59000 the round-7 body (h1 copied from P
+        // into X[8..15], the next set's P loads at the top), 59001 the first transpose stage of
+        // h1 reading P instead of the copies, 59002 the same in the general form, 59003
+        // production (copies, P loads after the small IFFT of h0), 59004 from P + late loads,
+        // 59005 / 59006 / 59007 = 59003 / 59004 / 59000 in the general form; 59030 / 59031 /
+        // 59033 / 59034 = 59000 / 59001 / 59003 / 59004 with the phase timeline (general form,
+        // as 51030)
+        case 59000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59001: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | kSplitFromP | kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59002: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<kSplitFromP | kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59003: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59004: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | kSplitFromP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59005: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<0>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59006: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<kSplitFromP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59007: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59030: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59031: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | kSplitFromP | kSplitTopP>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59033: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288>), dim3(grid), dim3(512), 0, st, p); break;
+        case 59034: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<524288 | kSplitFromP>), dim3(grid), dim3(512), 0, st, p); break;
         // XCD-affine queues (needs count % 8 == 0 and the host's zeroed 8-XCD queue words)
         case 57000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 134217728>), dim3(grid), dim3(512), 0, st, p); break;
         case 56000: hipLaunchKernelGGL((extend_gf8_bs128s_kernel<16777216 | 67108864>), dim3(grid), dim3(512), 0, st, p); break;

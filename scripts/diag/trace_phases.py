@@ -7,7 +7,9 @@ usage: python3 scripts/diag/trace_phases.py [mode ...]   (51030 production + tra
        51010 LDS-DMA form + trace, 51014 no global memory + trace, 51012 no arithmetic
        + trace; the exchange store path A/B: 58030 32-bit stores, 58031 32-bit stores +
        the tail of the large layers in the reads, 58032 = production, 58033 64-bit stores
-       + the tail in the reads)
+       + the tail in the reads; the top of the set A/B: 59030 the round-7 body, 59031
+       h1's first transpose stage from its landing registers, 59033 = production (the
+       next set's h1 loads after the small IFFT of h0), 59034 both)
 """
 import ctypes
 import json
