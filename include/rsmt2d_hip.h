@@ -451,9 +451,10 @@ int rsm_ns_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status, c
 int rsm_nmt_namespace_prove(const rsm_nmt_params* params, uint32_t index, const uint8_t* const* leaves,
                             uint32_t n_leaves, uint32_t leaf_size, const uint8_t* nid, uint8_t* record_out,
                             uint8_t* root_out);
-/* Verification of a namespace proof (host only): `shares` [n_shares][share_size] are the
- * shares presented with `record` for namespace `nid` of vector `index`, `root` the
- * committed root of the tree of n_leaves leaves.  *status, the first that applies: */
+/* Verification of a namespace proof (host form; the device form follows): `shares`
+ * [n_shares][share_size] are the shares presented with `record` for namespace `nid` of
+ * vector `index`, `root` the committed root of the tree of n_leaves leaves.  *status, the
+ * first that applies: */
 #define RSM_PROOF_NAMESPACE 5  /* INCLUSION: a leaf's wrapper namespace differs from nid;
                                   ABSENCE: the leaf node has min != max or min <= nid */
 #define RSM_PROOF_INCOMPLETE 6 /* a left node with max >= nid or a right node with min <= nid
@@ -474,6 +475,44 @@ int rsm_nmt_namespace_prove(const rsm_nmt_params* params, uint32_t index, const 
 int rsm_nmt_namespace_verify(const rsm_nmt_params* params, uint32_t index, const uint8_t* nid, const uint8_t* shares,
                              uint32_t n_shares, uint32_t share_size, uint32_t n_leaves, const uint8_t* record,
                              const uint8_t* root, uint32_t* status);
+/* Device form: n namespace proofs in one launch, one wave per query, on exactly what the
+ * producing calls write, so prove -> verify composes on the device with no repacking.
+ * d_records [n][rsm_ns_record_bytes(width, nmt)] (any alignment), d_offsets n + 1 uint32
+ * (4-byte aligned) and d_shares (16-byte aligned, shares_total shares of share_size
+ * bytes; NULL only with shares_total == 0) as rsm_ns_proofs_dev writes them; d_roots
+ * [count][2][width][2 * namespace_size + 32] as rsm_nmt_roots_squares_dev lays them out;
+ * d_status [n] uint32 (4-byte aligned).  `queries` and `nids` ([n][namespace_size]) are
+ * HOST memory, validated before anything is enqueued (RSM_EINVAL names the first query
+ * with square >= count, axis > 1 or index >= width) and copied before the call returns;
+ * n <= 2^20.
+ * Query i asks: is record i, with shares [d_offsets[i], d_offsets[i + 1]), a complete
+ * answer for nids[i] in vector (square, axis, index), under root (square, axis, index) of
+ * d_roots?  d_status[i] receives the word rsm_nmt_namespace_verify gives, with the same
+ * precedence (1 MALFORMED, 5 NAMESPACE, 6 INCOMPLETE, 2 ORDER, 3 ROOT, 0 OK), n_shares
+ * being d_offsets[i + 1] - d_offsets[i].  One device-only rule comes first: if
+ * d_offsets[i] > d_offsets[i + 1] or d_offsets[i + 1] > shares_total the status is
+ * MALFORMED and nothing of that query's shares or record is read.  A record of kind 3
+ * (RSM_NS_TREE) is MALFORMED, as on the host.
+ * The contract, as for single shares:
+ *   Positions are bound.  Node count, left and right counts and operand sides come from
+ *   (width, start, end), and only after the header has passed the MALFORMED checks
+ *   (start < end <= width, n_shares == end - start, ..); the record's n_nodes is only
+ *   compared with the derived count.
+ *   No address depends on record or share contents.  Share addresses come from d_offsets,
+ *   bounded by shares_total; node addresses are 16 + i * node_len for i below the derived
+ *   count (<= 2L); the leaf slot is at its fixed place and is read for ABSENCE only;
+ *   record bytes past the derived nodes are never read.
+ *   Writes.  Exactly one status word is written per query, and nothing else.
+ * No tree is built and no node store is needed: any 1 <= width <= 1024 is accepted, odd
+ * widths included (beyond: RSM_EUNSUPPORTED, a wave's LDS holds `width` nodes), and the
+ * quadrant rule uses square_size only.  namespace_size 1..32 (else RSM_EINVAL); nmt ==
+ * NULL: RSM_EUNSUPPORTED; share_size a multiple of 64 (else RSM_ESHARESIZE) and >=
+ * namespace_size (else RSM_ETREE).  RSM_EINVAL also for NULL or misaligned operands and
+ * n > 2^20.  n == 0 or count == 0 launches nothing.  Asynchronous on `stream`. */
+int rsm_ns_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets, const void* d_shares,
+                             uint64_t shares_total, const void* d_roots, uint32_t width, uint32_t share_size,
+                             uint32_t count, const rsm_nmt_params* nmt, const rsm_ns_query* queries,
+                             const uint8_t* nids, uint32_t n, void* d_status, void* stream);
 
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */

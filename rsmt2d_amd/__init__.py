@@ -35,6 +35,7 @@ __all__ = [
     "ErrUnrepairableDataSquare", "ErrUnevenChunks", "RSMError", "DeviceError",
     "library", "build", "device_context", "Proof", "Sample", "prove_samples_dev", "verify_samples_dev",
     "RSM_PROOF_OK", "RSM_PROOF_MALFORMED", "RSM_PROOF_ORDER", "RSM_PROOF_ROOT", "RSM_PROOF_OCCUPIED",
+    "RSM_PROOF_NAMESPACE", "RSM_PROOF_INCOMPLETE", "verify_namespaces_dev", "verify_namespace_data",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,6 +51,8 @@ RSM_OK, RSM_EINVAL, RSM_ESHARESIZE, RSM_ETOOFEW, RSM_ESHAPE, RSM_EDEVICE = 0, -1
 RSM_ENOMEM, RSM_EUNSUPPORTED, RSM_EUNREPAIRABLE, RSM_EBYZANTINE, RSM_ECELL, RSM_ETREE = -6, -7, -8, -9, -10, -11
 # proof verification status words (one per sample; the first condition that applies wins)
 RSM_PROOF_OK, RSM_PROOF_MALFORMED, RSM_PROOF_ORDER, RSM_PROOF_ROOT, RSM_PROOF_OCCUPIED = 0, 1, 2, 3, 4
+# namespace proofs only: a share of another namespace / shares of the namespace left out
+RSM_PROOF_NAMESPACE, RSM_PROOF_INCOMPLETE = 5, 6
 
 
 class RSMError(Exception):
@@ -214,6 +217,8 @@ SIGNATURES = {
     "rsm_nmt_namespace_prove": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _VP, _VP, _VP]),
     "rsm_nmt_namespace_verify": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _VP, _U32, _U32, _U32, _VP, _VP,
                                         ctypes.POINTER(_U32)]),
+    "rsm_ns_proofs_verify_dev": (_I32, [_VP, _VP, _VP, _VP, _U64, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP,
+                                        _U32, _VP, _VP]),
     "rsm_eds_namespace_proofs": (_I32, [_VP, _VP, _VP, _I32, _VP, _U32, _VP, _VP, _VP, _VP, _U64]),
     "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
 }
@@ -850,6 +855,87 @@ def prove_namespaces_dev(buf: "DeviceBuffer", width: int, share_size: int, queri
         for b in bufs:
             b.free()
     return _parse_ns_records(rec, offsets, sh, [q[2] for q in queries], width, share_size, nmt)
+
+
+def verify_namespaces_dev(records: "DeviceBuffer", offsets: "DeviceBuffer", shares: Optional["DeviceBuffer"],
+                          shares_total: int, roots: "DeviceBuffer", width: int, share_size: int,
+                          queries: Sequence[tuple], nids: Sequence[bytes], nmt: NmtParams, count: int = 1):
+    """Status words (RSM_PROOF_*) of ``(square, axis, index)`` queries, query i for
+    namespace ``nids[i]``, whose records, offsets and packed shares are device-resident as
+    rsm_ns_proofs_dev writes them, against ``roots`` ([count][2][width][root bytes], as
+    rsm_nmt_roots_squares_dev writes them): one rsm_ns_proofs_verify_dev launch, one wave
+    per query.  0 = these are all the shares of that namespace in that vector."""
+    import numpy as np
+    L, ctx, n = library(), records.ctx, len(queries)
+    if nmt is None:
+        raise RSMError(RSM_EUNSUPPORTED, "namespace proofs need the NMT")
+    ns = int(nmt.namespace_size)
+    if len(nids) != n or any(len(x) != ns for x in nids):
+        raise RSMError(RSM_EINVAL, "one namespace of namespace_size bytes per query")
+    out = np.zeros(n, np.uint32)
+    if n == 0:
+        return out
+    st = DeviceBuffer(n * 4)
+    try:
+        arr = (NsQuery * n)(*[NsQuery(*q) for q in queries])
+        _check(L.rsm_ns_proofs_verify_dev(ctx, records.ptr, offsets.ptr, shares.ptr if shares is not None else None,
+                                          shares_total, roots.ptr, width, share_size, count, ctypes.byref(nmt), arr,
+                                          b"".join(bytes(x) for x in nids), n, st.ptr, None))
+        _check(L.rsm_sync(ctx))
+        out[:] = st.download(n * 4).view(np.uint32)
+    finally:
+        st.free()
+    return out
+
+
+def verify_namespace_data(row_roots: Sequence[bytes], nid: bytes, data: Sequence[tuple], nmt: NmtParams, width: int,
+                          device: Optional[int] = 0) -> List[int]:
+    """The client side of ``ExtendedDataSquare.NamespaceData``: one RSM_PROOF_* status per
+    row of the square for the answer ``data`` (``(rowIdx, NamespaceProof)`` pairs) to
+    "every share of ``nid``", against the committed ``row_roots``.  A row absent from
+    ``data`` is an EMPTY claim and is checked as one: 0 when ``nid`` lies outside that
+    root's range, else 6 (shares were withheld).  All rows are verified in one
+    rsm_ns_proofs_verify_dev call on GPU ``device``; ``device=None`` runs
+    ``NamespaceProof.verify`` per row.  Results never depend on the path."""
+    import numpy as np
+    ns, nl = int(nmt.namespace_size), 2 * int(nmt.namespace_size) + 32
+    if len(row_roots) != width or any(len(r) != nl for r in row_roots) or len(nid) != ns:
+        raise RSMError(RSM_EINVAL, "one root of 2 * namespace_size + 32 bytes per row and a namespace of namespace_size bytes")
+    proofs = [NamespaceProof(NS_EMPTY, 0, 0, [], None, [], width, nmt, r) for r in range(width)]
+    for r, pr in data:
+        if not 0 <= r < width or pr.numLeaves != width:
+            raise RSMError(RSM_EINVAL, "a proof of a row or a tree that is not the square's")
+        proofs[r] = pr
+    if device is None:
+        out = []
+        for r, pr in enumerate(proofs):
+            row = NamespaceProof(pr.kind, pr.start, pr.end, pr.nodes, pr.leaf_node, pr.shares, width, nmt, r)
+            out.append(row.verify(row_roots[r], nid))
+        return out
+    sizes = {len(sh) for pr in proofs for sh in pr.shares}
+    if len(sizes) > 1:
+        raise RSMError(RSM_EINVAL, "shares of different sizes")
+    S = sizes.pop() if sizes else 64
+    offsets = np.cumsum([0] + [len(pr.shares) for pr in proofs]).astype(np.uint32)
+    total = int(offsets[-1])
+    packed = b"".join(b"".join(pr.shares) for pr in proofs)
+    roots = np.zeros((2, width, nl), np.uint8)  # the rows' roots; no column is asked
+    roots[0] = np.frombuffer(b"".join(bytes(r) for r in row_roots), np.uint8).reshape(width, nl)
+    recs = b"".join(pr.record() for pr in proofs)
+    bufs = [DeviceBuffer(len(recs), device), DeviceBuffer(offsets.nbytes, device), DeviceBuffer(max(total * S, 16), device),
+            DeviceBuffer(roots.nbytes, device)]
+    try:
+        bufs[0].upload(np.frombuffer(recs, np.uint8))
+        bufs[1].upload(offsets.view(np.uint8))
+        if total:
+            bufs[2].upload(np.frombuffer(packed, np.uint8))
+        bufs[3].upload(roots.reshape(-1))
+        st = verify_namespaces_dev(bufs[0], bufs[1], bufs[2], total, bufs[3], width, S, [(0, Row, r) for r in range(width)],
+                                   [bytes(nid)] * width, nmt)
+        return [int(x) for x in st]
+    finally:
+        for b in bufs:
+            b.free()
 
 
 # ---------------------------------------------------------------------------

@@ -23,7 +23,9 @@
 //                     lays its node message out in its own LDS bytes and hashes it.
 // Also nmt_nodes_kernel (every node kept: the proofs' node store) and
 // nmt_proof_verify_kernel (one lane per sampled share: leaf, fold of its proof through
-// hash_node, compare with the committed root; any width up to 65536).
+// hash_node, compare with the committed root; any width up to 65536) and
+// nmt_ns_verify_kernel (one wave per namespace proof: the leaves of its range, the fold of
+// its range proof in the wave's LDS, the completeness checks; any width up to 1024).
 // Namespace sizes up to 32 bytes (Celestia: 29), widths up to 1024 (LDS permitting).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -1034,6 +1036,195 @@ __global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __
     status[t] = !ordered ? kProofOrder : (diff ? kProofRoot : kProofOk);
 }
 
+// ---------------------------------------------------------------------------
+// Namespace proof verification (rsm_kernels.hpp "Namespace proof verification"): one WAVE
+// per query -- a query hashes end - start leaves and folds a tree over them, so one lane
+// per query (as above) would leave a wave waiting for its longest range.  The wave's LDS
+// holds one tree level in place, node p of a level at entry p (W entries of kNodeWords
+// words and a spare one), then, NS = 0, the 64 lanes' message bytes.  No workgroup barrier
+// anywhere: the waves of a workgroup share nothing and finish at different times; a wave
+// orders its own LDS traffic as nmt_tree_wave_kernel does (wave_sync between a pass's
+// reads and its in-place writes and after every level).
+//   header : every lane reads the two offsets, the 16-byte header, the query and the root;
+//            wave-uniform exits follow rsm_nmt_namespace_verify's precedence (merkle.cpp)
+//   leaves : lane j hashes shares start + j, + 64, .. into entries start + j ..; ABSENCE:
+//            entry start is the record's leaf node
+//   nodes  : lane i < the derived count checks proof node i against nid (INCOMPLETE)
+//   fold   : level l grafts the left proof node at entry a - 1 when a is odd and the
+//            right one at last + 1 when last is even and below the level's last node; lane
+//            j joins entries a + 2j and a + 2j + 1 into entry a / 2 + j (both reads at or
+//            past the write: a level's reads precede its writes), an unpaired last entry is
+//            carried up; a >>= 1, last >>= 1.  Left nodes are taken from n_left - 1
+//            downward, right ones from n_left upward.
+// Counts, sides and every address come from (W, start, end) and the offsets, after the
+// header passed the MALFORMED checks; nothing of a record past its derived nodes (and, for
+// ABSENCE, the leaf slot) is read.
+template <int NS>
+__device__ __forceinline__ uint32_t ns_verify_query(const uint8_t* __restrict__ rec, const uint32_t* __restrict__ offsets,
+                                                    const uint8_t* __restrict__ shares, uint64_t shares_total,
+                                                    const uint8_t* __restrict__ roots, uint32_t W, uint32_t S, uint32_t ns,
+                                                    uint32_t k, bool ig, const NsQuery& qu, uint32_t lane,
+                                                    uint32_t* __restrict__ row, uint8_t* __restrict__ mb) {
+    uint32_t* const spare = row + (size_t)W * kNodeWords;  // entry W: what lanes past a pass's last node store
+    const uint32_t o0 = __builtin_amdgcn_readfirstlane(offsets[0]), o1 = __builtin_amdgcn_readfirstlane(offsets[1]);
+    if (o0 > o1 || o1 > shares_total) return kProofMalformed;  // nothing of the record or the shares is read
+    const uint32_t n_shares = o1 - o0, L = proof_levels(W), NL = 2u * ns + 32u;
+    const uint32_t kind = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec)),
+                   start = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 4)),
+                   end = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 8)),
+                   n_nodes = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 12));
+    Node rt;
+    node_from_bytes<NS>(roots + (((uint64_t)qu.square * 2u + qu.axis) * W + qu.index) * NL, ns, rt);
+    // 1. the header against what (W, start, end) dictates
+    if (kind == kNsEmpty) {
+        if (start | end | n_nodes | n_shares) return kProofMalformed;
+        return !ns_less(qu.nid, rt.mn) && !ns_less(rt.mx, qu.nid) ? kProofIncomplete : kProofOk;
+    }
+    if (kind == kNsInclusion) {
+        if (!(start < end && end <= W) || n_shares != end - start) return kProofMalformed;
+    } else if (kind == kNsAbsence) {
+        if (start >= W || end != start + 1u || n_shares != 0u) return kProofMalformed;
+    } else {
+        return kProofMalformed;  // kNsTree among them
+    }
+    uint32_t n_left = 0;
+    const uint32_t nn = ns_range_nodes(W, start, end, &n_left);
+    if (n_nodes != nn) return kProofMalformed;
+    // 2. the leaves carry nid / the absence leaf is one leaf above nid
+    bool flag = false;
+    if (kind == kNsInclusion) {
+        // Every lane hashes in every pass, here and in the fold: past the pass's last leaf
+        // (node) a lane repeats leaf i0 + lane % rem and stores it to the spare entry (a
+        // wave with few lanes active runs its SHA rounds 2-3.5x slower per compression:
+        // kernels_sha.hip; the store keeps the compiler from shrinking the hash to the
+        // owning lanes).
+        for (uint32_t i0 = 0; i0 < n_shares; i0 += 64u) {
+            const uint32_t rem = n_shares - i0;
+            const bool own = lane < rem;
+            const uint32_t i = i0 + (own ? lane : lane % rem);
+            const uint8_t* sp = shares + ((uint64_t)o0 + i) * S;
+            const bool q0 = qu.index < k && start + i < k;
+            Node lf;
+            if constexpr (NS == 29) verify_leaf29(sp, S, q0, lf);
+            else verify_leaf(sp, S, ns, q0, lf);
+            bool differs = false;
+#pragma unroll
+            for (int w = 0; w < (int)kNsWords; ++w) differs |= lf.mn[w] != qu.nid[w];
+            flag |= own && differs;
+            lds_store(own ? row + (size_t)(start + i) * kNodeWords : spare, lf);
+        }
+    } else {
+        Node lf;
+        node_from_bytes<NS>(rec + 16u + 2u * L * NL, ns, lf);
+#pragma unroll
+        for (int w = 0; w < (int)kNsWords; ++w) flag |= lf.mn[w] != lf.mx[w];
+        flag |= !ns_less(qu.nid, lf.mn);
+        if (lane == 0) lds_store(row + (size_t)start * kNodeWords, lf);
+    }
+    if (__ballot(flag)) return kProofNamespace;
+    // 3. nothing of nid lies under a proof node (nn <= 2 L < 64)
+    if (lane < nn) {
+        Node nd;
+        node_from_bytes<NS>(rec + 16u + lane * NL, ns, nd);
+        flag = lane < n_left ? !ns_less(nd.mx, qu.nid) : !ns_less(qu.nid, nd.mn);
+    }
+    if (__ballot(flag)) return kProofIncomplete;
+    // 4, 5. the fold
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    auto hash = [&](const Node& a, const Node& b, Node& o) -> bool {
+        if constexpr (NS == 0) {
+            return hash_node(a, b, ns, ig, mb, o);
+        } else {
+            static_assert(NS == 0 || WNode<NS>::kW == (int)kNsWords, "a WNode laid out as a Node");
+            WNode<NS> x, y, z;
+#pragma unroll
+            for (int i = 0; i < (int)kNsWords; ++i) x.mn[i] = a.mn[i], x.mx[i] = a.mx[i], y.mn[i] = b.mn[i], y.mx[i] = b.mx[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) x.d[i] = a.d[i], y.d[i] = b.d[i];
+            const bool ok = hash_node_w<NS>(x, y, ig, z);
+#pragma unroll
+            for (int i = 0; i < (int)kNsWords; ++i) o.mn[i] = z.mn[i], o.mx[i] = z.mx[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o.d[i] = z.d[i];
+            return ok;
+        }
+    };
+    uint32_t a = start, last = end - 1u, li = n_left, ri = n_left;  // next left node: li - 1; next right: ri
+    for (uint32_t l = 0; l < L; ++l) {
+        if (a & 1u) {
+            --li;
+            --a;
+            if (lane == 0) {
+                Node nd;
+                node_from_bytes<NS>(rec + 16u + li * NL, ns, nd);
+                lds_store(row + (size_t)a * kNodeWords, nd);
+            }
+        }
+        if (!(last & 1u) && last + 1u < proof_level_count(W, l)) {
+            ++last;
+            if (lane == 0) {
+                Node nd;
+                node_from_bytes<NS>(rec + 16u + ri * NL, ns, nd);
+                lds_store(row + (size_t)last * kNodeWords, nd);
+            }
+            ++ri;
+        }
+        wave_sync();  // the leaves / the level below and the grafts are written
+        const uint32_t have = last - a + 1u, np = have / 2u, up = np + (have & 1u);  // a is even
+        for (uint32_t v0 = 0; v0 < up; v0 += 64u) {
+            const uint32_t rem = up - v0;
+            const bool own = lane < rem;
+            const uint32_t j = v0 + (own ? lane : lane % rem);
+            Node x, o;
+            lds_node(row + (size_t)(a + 2u * j) * kNodeWords, x);
+            if (j < np) {
+                Node y;
+                lds_node(row + (size_t)(a + 2u * j + 1u) * kNodeWords, y);
+                if (!hash(x, y, o) && own) flag = true;
+            } else {
+                o = x;  // carried up unchanged
+            }
+            wave_sync();  // every lane's reads of this pass before any write (a / 2 + j <= a + 2 j)
+            lds_store(own ? row + (size_t)(a / 2u + j) * kNodeWords : spare, o);
+        }
+        a >>= 1;
+        last >>= 1;
+    }
+    wave_sync();
+    if (__ballot(flag)) return kProofOrder;
+    Node acc;
+    lds_node(row, acc);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int w = 0; w < (int)kNsWords; ++w) diff |= (acc.mn[w] ^ rt.mn[w]) | (acc.mx[w] ^ rt.mx[w]) | (acc.d[w] ^ rt.d[w]);
+    return diff ? kProofRoot : kProofOk;
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_ns_verify_kernel(const uint8_t* __restrict__ records,
+                                                            const uint32_t* __restrict__ offsets,
+                                                            const uint8_t* __restrict__ shares, uint64_t shares_total,
+                                                            const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
+                                                            uint32_t ns, uint32_t k, uint32_t ignore_max,
+                                                            const NsQuery* __restrict__ queries, uint32_t n,
+                                                            uint32_t record_bytes, uint32_t wave_words,
+                                                            uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // per wave: W nodes and a spare one, then (NS == 0) the lanes' node messages
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * (blockDim.x >> 6) + wv;
+    if (q >= n) return;
+    uint32_t* const row = lds + (size_t)wv * wave_words;
+    uint8_t* const mb = reinterpret_cast<uint8_t*>(row + (size_t)(W + 1u) * kNodeWords) + (NS == 0 ? lane * (64u * node_blocks(ns)) : 0u);
+    const NsQuery qu = queries[q];
+    const uint32_t st = ns_verify_query<NS>(records + (uint64_t)q * record_bytes, offsets + q, shares, shares_total, roots, W,
+                                            S, ns, k, ignore_max != 0, qu, lane, row, mb);
+    if (lane == 0) status[q] = st;
+}
+
 }  // namespace
 
 hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
@@ -1047,6 +1238,38 @@ hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_rec
     else
         hipLaunchKernelGGL(nmt_proof_verify_kernel<0>, grid, dim3(256), (size_t)256 * 64u * node_blocks(ns), st, d_shares,
                            d_records, d_roots, W, S, ns, k, ignore_max, d_samples, n, d_status);
+    return hipGetLastError();
+}
+
+bool nmt_ns_verify_supported(uint32_t W, uint32_t ns) { return W >= 1 && W <= kMaxWidth && ns >= 1 && ns <= kMaxNs; }
+
+// One wave per query, up to four waves per workgroup: the count that lets most waves share
+// a CU's LDS (W = 256: 24 KiB a wave, six waves per CU as two workgroups of three;
+// W = 1024, ns = 32: 112 KiB, one wave).
+hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                                uint64_t shares_total, const uint8_t* d_roots, uint32_t W, uint32_t S, uint32_t ns,
+                                uint32_t k, uint32_t ignore_max, const NsQuery* d_queries, uint32_t n, uint32_t* d_status,
+                                hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (!nmt_ns_verify_supported(W, ns)) return hipErrorInvalidValue;
+    const bool f29 = ns == 29 && S % 64 == 0 && S >= 64;
+    const uint32_t wave_words = (W + 1u) * kNodeWords + (f29 ? 0u : 64u * 16u * node_blocks(ns));
+    const size_t wave_bytes = (size_t)wave_words * 4u;
+    uint32_t wpb = 1, best = 0;
+    for (uint32_t b = 1; b <= 4; ++b) {
+        if (b * wave_bytes > kLdsCap) break;
+        const uint32_t waves = (uint32_t)(kLdsCap / (b * wave_bytes)) * b;  // per CU
+        if (waves >= best) best = waves, wpb = b;
+    }
+    if (best == 0) return hipErrorInvalidValue;
+    const uint32_t record_bytes = 16u + (2u * proof_levels(W) + 1u) * (2u * ns + 32u);
+    const dim3 grid((n + wpb - 1) / wpb);
+    if (f29)
+        hipLaunchKernelGGL(nmt_ns_verify_kernel<29>, grid, dim3(64 * wpb), wpb * wave_bytes, st, d_records, d_offsets, d_shares,
+                           shares_total, d_roots, W, S, ns, k, ignore_max, d_queries, n, record_bytes, wave_words, d_status);
+    else
+        hipLaunchKernelGGL(nmt_ns_verify_kernel<0>, grid, dim3(64 * wpb), wpb * wave_bytes, st, d_records, d_offsets, d_shares,
+                           shares_total, d_roots, W, S, ns, k, ignore_max, d_queries, n, record_bytes, wave_words, d_status);
     return hipGetLastError();
 }
 

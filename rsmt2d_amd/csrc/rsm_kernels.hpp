@@ -268,6 +268,22 @@ hipError_t launch_proof_verify(const uint8_t* d_shares, const uint8_t* d_records
 hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
                                    uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max, const ProofSample* d_samples,
                                    uint32_t n, uint32_t* d_status, hipStream_t st);
+// Namespace proof verification (DESIGN.md §4 "Namespace proofs"; kernels_nmt.hip): one
+// wave per query.  Query i: is record i (d_records: [n][16 + (2L + 1) * node_len], any
+// alignment) with shares [d_offsets[i], d_offsets[i + 1]) of d_shares (16-byte aligned,
+// shares_total shares) a complete answer for d_queries[i].nid in vector (square, axis,
+// index), under root (square, axis, index) of d_roots?  d_status[n] receives a kProof*
+// word with rsm_nmt_namespace_verify's precedence; offsets that decrease or pass
+// shares_total give kProofMalformed before anything else of the query is read.  Counts,
+// operand sides and every address come from (W, start, end) and the offsets, never from
+// what a record or a share holds.  1 <= W <= 1024 (a wave's LDS holds W nodes); every
+// query must be in range (the host validates them).
+constexpr uint32_t kProofNamespace = 5, kProofIncomplete = 6;
+bool nmt_ns_verify_supported(uint32_t W, uint32_t ns);
+hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                                uint64_t shares_total, const uint8_t* d_roots, uint32_t W, uint32_t S, uint32_t ns,
+                                uint32_t k, uint32_t ignore_max, const NsQuery* d_queries, uint32_t n, uint32_t* d_status,
+                                hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

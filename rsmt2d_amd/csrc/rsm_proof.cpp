@@ -4,7 +4,9 @@
 // store; host restatements of merkle.cpp otherwise); the receiving side:
 // rsm_proofs_verify_dev over the verify kernels (kernels_sha.hip, kernels_nmt.hip) and
 // rsm_eds_import_samples (verify, then SetCell); namespace proofs: rsm_ns_proofs_dev over
-// kernels_nsproof.hip and rsm_eds_namespace_proofs.  Formats: include/rsmt2d_hip.h.
+// kernels_nsproof.hip, rsm_eds_namespace_proofs, and their receiving side
+// rsm_ns_proofs_verify_dev over nmt_ns_verify_kernel (kernels_nmt.hip).  Formats:
+// include/rsmt2d_hip.h.
 #include "eds_internal.hpp"
 
 #include <algorithm>
@@ -20,7 +22,8 @@ static_assert(sizeof(NsQuery) == 44 && kNsEmpty == RSM_NS_EMPTY && kNsInclusion 
               "the kernels' namespace proof kinds are the C ABI's");
 
 static_assert(kProofOk == RSM_PROOF_OK && kProofMalformed == RSM_PROOF_MALFORMED && kProofOrder == RSM_PROOF_ORDER &&
-                  kProofRoot == RSM_PROOF_ROOT,
+                  kProofRoot == RSM_PROOF_ROOT && kProofNamespace == RSM_PROOF_NAMESPACE &&
+                  kProofIncomplete == RSM_PROOF_INCOMPLETE,
               "the kernels' status words are the C ABI's");
 
 namespace {
@@ -410,6 +413,49 @@ int rsm_ns_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status, c
                                           static_cast<uint32_t*>(d_offsets), static_cast<uint8_t*>(d_shares), shares_cap,
                                           st);
     return e == hipSuccess ? RSM_OK : hip_fail(e, "namespace proof kernel launch");
+}
+
+int rsm_ns_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets, const void* d_shares,
+                             uint64_t shares_total, const void* d_roots, uint32_t width, uint32_t share_size,
+                             uint32_t count, const rsm_nmt_params* nmt, const rsm_ns_query* queries,
+                             const uint8_t* nids, uint32_t n, void* d_status, void* stream) {
+    if (!ctx || width == 0 ||
+        (n && count && (!queries || !nids || !d_records || !d_offsets || !d_roots || !d_status || (shares_total && !d_shares))))
+        return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: bad arguments");
+    if (!nmt) return fail(RSM_EUNSUPPORTED, "rsm_ns_proofs_verify_dev: the DefaultTree has no namespaces");
+    if (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0)
+        return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: namespace size %u (1..32) or square size 0", nmt->namespace_size);
+    if (reinterpret_cast<uintptr_t>(d_shares) & 15u)
+        return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: d_shares must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: d_offsets and d_status must be 4-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (!nmt_ns_verify_supported(width, nmt->namespace_size))
+        return fail(RSM_EUNSUPPORTED, "rsm_ns_proofs_verify_dev: width %u not supported (at most 1024)", width);
+    if (share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (n > (1u << 20)) return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: at most %u queries per call", 1u << 20);
+    if (n == 0 || count == 0) return RSM_OK;
+    const uint32_t ns = nmt->namespace_size;
+    std::vector<NsQuery> q(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (queries[i].square >= count || queries[i].axis > 1 || queries[i].index >= width)
+            return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: query %u (square %u, axis %u, index %u) is out of range", i,
+                        queries[i].square, queries[i].axis, queries[i].index);
+        q[i] = NsQuery{queries[i].square, queries[i].axis, queries[i].index, {}};
+        for (uint32_t b = 0; b < ns; ++b)  // big-endian words, zero padded, as rsm_ns_proofs_dev stages them
+            q[i].nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
+    }
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const void* dq = nullptr;
+    if (int rc = stage_bytes(st, ss, q.data(), (size_t)n * sizeof(NsQuery), &dq)) return rc;
+    const hipError_t e = launch_nmt_ns_verify(
+        static_cast<const uint8_t*>(d_records), static_cast<const uint32_t*>(d_offsets), static_cast<const uint8_t*>(d_shares),
+        shares_total, static_cast<const uint8_t*>(d_roots), width, share_size, ns, nmt->square_size,
+        nmt->ignore_max_namespace, static_cast<const NsQuery*>(dq), n, static_cast<uint32_t*>(d_status), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "namespace proof verify kernel launch");
 }
 
 int rsm_eds_namespace_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, int axis, const uint32_t* indices,
