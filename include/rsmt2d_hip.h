@@ -388,6 +388,94 @@ int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t 
 int rsm_nmt_tree_verify(const rsm_nmt_params* params, uint32_t index, const uint8_t* share, uint32_t share_size,
                         uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root, uint32_t* status);
 
+/* ---- data root --------------------------------------------------------------------- */
+/* What commits the roots: the one 32-byte hash a block header carries.  It is the
+ * RFC 6962 Merkle root over rowRoots ++ colRoots (tendermint HashFromByteSlices,
+ * Celestia's DataAvailabilityHeader.Hash(); the roots nmtwrapper_test.go:79 speaks of).
+ *
+ * The tree is the level picture of "share inclusion proofs" above over N = 2 * width
+ * leaves: leaf t is the root bytes of tree t as the roots calls lay them out (rows
+ * 0 .. W-1, then columns W .. 2W-1), root_len = 32 (DefaultTree) or
+ * 2 * namespace_size + 32 (NMT) bytes each.
+ *   leaf hash  SHA-256(0x00 || root bytes)
+ *   inner node SHA-256(0x01 || l || r)
+ *   an unpaired last node is carried up unchanged
+ * which equals RFC 6962's recursive split at the largest power of two below n.  Every
+ * node is a 32-byte digest at every level, over NMT roots too.  The proof record of a
+ * root keeps the share proofs' format with node_len = 32 and L2 = ceil(log2(2 * width))
+ * levels: uint32 n_nodes | uint32 right_mask | nodes bottom-up | zeros, fixed stride
+ * rsm_data_root_record_bytes = 8 + L2 * 32. */
+typedef struct {
+    uint32_t square; /* square of a batch */
+    uint32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */
+    uint32_t index;  /* row or column: leaf axis * width + index of the data-root tree */
+} rsm_root_ref;
+/* Bytes of one root proof record (any width >= 1; 0 for width 0). */
+uint32_t rsm_data_root_record_bytes(uint32_t width);
+/* Bytes of the node store of `count` data-root trees (opaque to callers: the leaf digests
+ * and every upper node); 0 beyond the build's width limit (1 <= width <= 2048). */
+uint64_t rsm_data_root_nodes_bytes(uint32_t width, uint32_t count);
+/* The data roots of `count` squares: d_roots (device, any alignment) is
+ * [count][2][width][root_len], exactly as rsm_roots_squares_dev /
+ * rsm_nmt_roots_squares_dev / rsm_proof_nodes_dev write it; d_data_roots (device, any
+ * alignment) receives [count][32]; d_nodes (device, nullable, 16-byte aligned,
+ * rsm_data_root_nodes_bytes) the node store.  root_len is any value 32 .. 96
+ * (RSM_EINVAL otherwise): the leaf is the raw bytes, so the call does not need to know
+ * which tree made them.  1 <= width <= 2048, every width for which device roots exist;
+ * beyond that RSM_EUNSUPPORTED.  count == 0 launches nothing.  No scratch beyond d_nodes.
+ * Asynchronous on `stream`. */
+int rsm_data_roots_dev(rsm_ctx* ctx, const void* d_roots, uint32_t width, uint32_t root_len, uint32_t count,
+                       void* d_data_roots, void* d_nodes, void* stream);
+/* n root proof records out of a node store: record i (d_records: device, any alignment,
+ * stride rsm_data_root_record_bytes) is the proof of leaf axis * width + index of square
+ * `square`.  `refs` is HOST memory, validated before anything is enqueued (RSM_EINVAL
+ * names the first ref with square >= count, axis > 1 or index >= width) and copied before
+ * the call returns (n <= 2^24).  The records are written asynchronously on `stream`. */
+int rsm_root_proofs_dev(rsm_ctx* ctx, const void* d_nodes, uint32_t width, uint32_t count, const rsm_root_ref* refs,
+                        uint32_t n, void* d_records, void* stream);
+/* The chained verifier: share -> row/column root -> data root, with no root table.
+ * Sample i takes share i and record i as in rsm_proofs_verify_dev, and root record i
+ * (d_root_records: stride rsm_data_root_record_bytes(width), any alignment); it is
+ * checked against d_data_roots[square] (32 bytes each, any alignment).  The lane folds
+ * the share proof to a candidate root (DefaultTree: the digest; NMT: min || max ||
+ * digest), hashes that candidate as a leaf of the data-root tree, folds the root record
+ * and compares with the data root.  Status words, the first that applies:
+ *   RSM_PROOF_MALFORMED  the share record's header differs from what (width, pos) dictates
+ *   RSM_PROOF_MALFORMED  the root record's header differs from what
+ *                        (2 * width, axis * width + index) dictates
+ *   RSM_PROOF_ORDER      NMT share fold, as in rsm_proofs_verify_dev
+ *   RSM_PROOF_ROOT       the final digest differs from the data root
+ *   RSM_PROOF_OK
+ * Both header checks come before any hashing.  The contract of rsm_proofs_verify_dev
+ * holds for both records: positions are bound, counts and operand sides are derived and
+ * never read, bytes past the derived nodes are never read, no address depends on record
+ * or share contents, and exactly one status word is written per sample.  Limits and
+ * argument errors are those of rsm_proofs_verify_dev (no tree is built): 1 <= width <=
+ * 65536, namespace_size 1..32, share_size a multiple of 64 (NMT: >= namespace_size, else
+ * RSM_ETREE), n <= 2^24; n == 0 or count == 0 launches nothing.  Asynchronous on
+ * `stream`. */
+int rsm_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_shares, const void* d_records, const void* d_root_records,
+                                    const void* d_data_roots, uint32_t width, uint32_t share_size, uint32_t count,
+                                    const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n, void* d_status,
+                                    void* stream);
+/* Host restatements (merkle.cpp), any width >= 1.  roots: [2][width][root_len], root_len
+ * 1 .. 96 here (the host hashes any length).  rsm_data_root: the data root.
+ * rsm_data_root_prove: the record of leaf axis * width + index into record_out
+ * (rsm_data_root_record_bytes(width)).  rsm_data_root_verify: root_bytes (root_len bytes)
+ * as that leaf under data_root; *status MALFORMED / ROOT / OK.
+ * rsm_sample_verify_data_root: the chained verifier for one sample (its `square` is not
+ * used), nmt == NULL the DefaultTree; the same semantics and status words as the device
+ * form.  The return value is an argument error only (RSM_EINVAL; RSM_ETREE for a share
+ * shorter than the namespace). */
+int rsm_data_root(const uint8_t* roots, uint32_t width, uint32_t root_len, uint8_t* out);
+int rsm_data_root_prove(const uint8_t* roots, uint32_t width, uint32_t root_len, uint32_t axis, uint32_t index,
+                        uint8_t* record_out);
+int rsm_data_root_verify(const uint8_t* root_bytes, uint32_t root_len, uint32_t width, uint32_t axis, uint32_t index,
+                         const uint8_t* record, const uint8_t* data_root, uint32_t* status);
+int rsm_sample_verify_data_root(const rsm_nmt_params* nmt, uint32_t width, const rsm_sample* sample, const uint8_t* share,
+                                uint32_t share_size, const uint8_t* record, const uint8_t* root_record,
+                                const uint8_t* data_root, uint32_t* status);
+
 /* ---- namespace proofs -------------------------------------------------------------- */
 /* "Every share of namespace nid in this row (or column), with proof that these are all
  * of them": nmt's ProveNamespace / VerifyNamespace (celestia-node's GetSharesByNamespace
@@ -542,6 +630,14 @@ int rsm_eds_flattened(const rsm_eds* eds, uint8_t* out, uint8_t* present);
 /* RowRoots()/ColRoots() (:258-280): width roots of root_cap bytes each. */
 int rsm_eds_roots(rsm_eds* eds, int axis, rsm_tree_root_fn tree_fn, void* user, uint8_t* roots_out,
                   uint32_t root_cap, uint32_t* root_len);
+
+/* The square's data root ("data root" above) into out[32]: the row and column roots by
+ * the path rsm_eds_roots takes, then the root over rowRoots ++ colRoots.  With a context
+ * and a complete square of a supported width the roots stay on the device and
+ * rsm_data_roots_dev hashes them there; otherwise the host restatement runs.  root_len
+ * is whatever the tree returns, at most 96 bytes.  Errors as rsm_eds_roots.  Results
+ * never depend on the path. */
+int rsm_eds_data_root(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, uint8_t* out);
 
 /* Proofs of n samples (square = 0) of this square: n records of
  * rsm_proof_record_bytes(width, nmt) into records_out, the n shares into shares_out

@@ -36,6 +36,7 @@ __all__ = [
     "library", "build", "device_context", "Proof", "Sample", "prove_samples_dev", "verify_samples_dev",
     "RSM_PROOF_OK", "RSM_PROOF_MALFORMED", "RSM_PROOF_ORDER", "RSM_PROOF_ROOT", "RSM_PROOF_OCCUPIED",
     "RSM_PROOF_NAMESPACE", "RSM_PROOF_INCOMPLETE", "verify_namespaces_dev", "verify_namespace_data",
+    "RootRef", "RootProof", "data_roots_dev", "prove_roots_dev", "verify_samples_data_root_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -221,6 +222,18 @@ SIGNATURES = {
                                         _U32, _VP, _VP]),
     "rsm_eds_namespace_proofs": (_I32, [_VP, _VP, _VP, _I32, _VP, _U32, _VP, _VP, _VP, _VP, _U64]),
     "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
+    "rsm_data_root_record_bytes": (_U32, [_U32]),
+    "rsm_data_root_nodes_bytes": (_U64, [_U32, _U32]),
+    "rsm_data_roots_dev": (_I32, [_VP, _VP, _U32, _U32, _U32, _VP, _VP, _VP]),
+    "rsm_root_proofs_dev": (_I32, [_VP, _VP, _U32, _U32, _VP, _U32, _VP, _VP]),
+    "rsm_proofs_verify_data_root_dev": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP,
+                                               _U32, _VP, _VP]),
+    "rsm_data_root": (_I32, [_VP, _U32, _U32, _VP]),
+    "rsm_data_root_prove": (_I32, [_VP, _U32, _U32, _U32, _U32, _VP]),
+    "rsm_data_root_verify": (_I32, [_VP, _U32, _U32, _U32, _U32, _VP, _VP, ctypes.POINTER(_U32)]),
+    "rsm_sample_verify_data_root": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _VP, _U32, _VP, _VP, _VP,
+                                           ctypes.POINTER(_U32)]),
+    "rsm_eds_data_root": (_I32, [_VP, _VP, _VP, _VP]),
 }
 
 
@@ -739,6 +752,121 @@ def verify_samples_dev(shares: "DeviceBuffer", records: "DeviceBuffer", roots: "
 
 
 # ---------------------------------------------------------------------------
+# Data root (include/rsmt2d_hip.h "data root")
+# ---------------------------------------------------------------------------
+class RootRef(ctypes.Structure):
+    """rsm_root_ref: the root of row (axis 0) / column (axis 1) ``index`` of ``square``."""
+    _fields_ = [("square", ctypes.c_uint32), ("axis", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+
+class RootProof:
+    """The proof of one row or column root under a square's data root (the RFC 6962 root
+    over rowRoots ++ colRoots, DataAvailabilityHeader.Hash()).
+
+    ``nodes``: the 32-byte siblings bottom-up; ``right_mask``: bit i set when ``nodes[i]``
+    is the right operand of its parent hash; ``axis`` / ``index``: the root proven, leaf
+    ``axis * width + index`` of the tree over ``2 * width`` roots."""
+
+    def __init__(self, nodes: List[bytes], right_mask: int, axis: int, index: int, width: int):
+        self.nodes, self.right_mask, self.axis, self.index, self.width = nodes, right_mask, axis, index, width
+
+    def record(self) -> bytes:
+        """The root proof record (include/rsmt2d_hip.h): u32 n_nodes | u32 right_mask | the
+        nodes | zeros up to 8 + ceil(log2(2 width)) * 32 bytes."""
+        rb = 8 + (2 * self.width - 1).bit_length() * 32
+        body = len(self.nodes).to_bytes(4, "little") + self.right_mask.to_bytes(4, "little") + b"".join(self.nodes)
+        if len(body) > rb or any(len(nd) != 32 for nd in self.nodes):
+            raise RSMError(RSM_EINVAL, "proof nodes do not fit the data-root tree's record")
+        return body + bytes(rb - len(body))
+
+    def verify(self, root_bytes: bytes, data_root: bytes) -> int:
+        """The status word (RSM_PROOF_*) of ``root_bytes`` as this proof's leaf under
+        ``data_root`` (rsm_data_root_verify)."""
+        st = ctypes.c_uint32(0)
+        _check(library().rsm_data_root_verify(bytes(root_bytes), len(root_bytes), self.width, self.axis, self.index,
+                                              self.record(), bytes(data_root), ctypes.byref(st)))
+        return int(st.value)
+
+
+def _parse_root_records(rec: bytes, refs, width: int) -> List[RootProof]:
+    """RootProof objects from n root proof records; refs: (axis, index)."""
+    rb = 8 + (2 * width - 1).bit_length() * 32
+    out = []
+    for i, (axis, index) in enumerate(refs):
+        r = rec[i * rb:(i + 1) * rb]
+        n_nodes, mask = int.from_bytes(r[0:4], "little"), int.from_bytes(r[4:8], "little")
+        out.append(RootProof([r[8 + j * 32: 8 + (j + 1) * 32] for j in range(n_nodes)], mask, axis, index, width))
+    return out
+
+
+def data_roots_dev(roots_buf: "DeviceBuffer", width: int, root_len: int, count: int, want_nodes: bool = False):
+    """The data roots of ``count`` squares whose roots ([count][2][width][root_len], as the
+    roots calls write them) are device-resident in ``roots_buf``: one rsm_data_roots_dev
+    launch.  Returns a (count, 32) uint8 array; with ``want_nodes`` also the node store (a
+    DeviceBuffer the caller frees) for ``prove_roots_dev``."""
+    import numpy as np
+    L, ctx = library(), roots_buf.ctx
+    nbytes = int(L.rsm_data_root_nodes_bytes(width, count)) if want_nodes else 0
+    if want_nodes and nbytes == 0 and count:
+        raise RSMError(RSM_EUNSUPPORTED, f"device data roots: width {width} not supported")
+    out = DeviceBuffer(max(count * 32, 16))
+    nodes = DeviceBuffer(max(nbytes, 16)) if want_nodes else None
+    try:
+        _check(L.rsm_data_roots_dev(ctx, roots_buf.ptr, width, root_len, count, out.ptr,
+                                    nodes.ptr if nodes is not None else None, None))
+        _check(L.rsm_sync(ctx))
+        got = out.download(max(count * 32, 16))[:count * 32].reshape(count, 32).copy()
+    except Exception:
+        if nodes is not None:
+            nodes.free()
+        raise
+    finally:
+        out.free()
+    return (got, nodes) if want_nodes else got
+
+
+def prove_roots_dev(nodes: "DeviceBuffer", width: int, refs: Sequence[tuple], count: int = 1) -> List[RootProof]:
+    """Proofs of the ``(square, axis, index)`` roots out of the node store that
+    ``data_roots_dev(..., want_nodes=True)`` returned: one rsm_root_proofs_dev gather."""
+    L, ctx, n = library(), nodes.ctx, len(refs)
+    rb = int(L.rsm_data_root_record_bytes(width))
+    recs = DeviceBuffer(max(n * rb, 16))
+    try:
+        arr = (RootRef * max(n, 1))(*[RootRef(*r) for r in refs])
+        _check(L.rsm_root_proofs_dev(ctx, nodes.ptr, width, count, arr, n, recs.ptr, None))
+        _check(L.rsm_sync(ctx))
+        rec = recs.download(max(n * rb, 16)).tobytes()
+    finally:
+        recs.free()
+    return _parse_root_records(rec, [r[1:] for r in refs], width)
+
+
+def verify_samples_data_root_dev(shares: "DeviceBuffer", records: "DeviceBuffer", root_records: "DeviceBuffer",
+                                 data_roots: "DeviceBuffer", width: int, share_size: int, samples: Sequence[tuple],
+                                 nmt: Optional[NmtParams] = None, count: int = 1):
+    """Status words (RSM_PROOF_*) of ``(square, axis, index, pos)`` samples checked all the
+    way to their square's data root, with no root table: shares, share proof records and
+    root proof records device-resident as rsm_proofs_dev / rsm_root_proofs_dev write them,
+    ``data_roots`` [count][32]: one rsm_proofs_verify_data_root_dev launch."""
+    import numpy as np
+    L, ctx, n = library(), shares.ctx, len(samples)
+    out = np.zeros(n, np.uint32)
+    if n == 0:
+        return out
+    st = DeviceBuffer(n * 4)
+    try:
+        arr = (Sample * n)(*[Sample(*s) for s in samples])
+        _check(L.rsm_proofs_verify_data_root_dev(ctx, shares.ptr, records.ptr, root_records.ptr, data_roots.ptr, width,
+                                                 share_size, count, ctypes.byref(nmt) if nmt is not None else None, arr,
+                                                 n, st.ptr, None))
+        _check(L.rsm_sync(ctx))
+        out[:] = st.download(n * 4).view(np.uint32)
+    finally:
+        st.free()
+    return out
+
+
+# ---------------------------------------------------------------------------
 # Namespace proofs (include/rsmt2d_hip.h "namespace proofs")
 # ---------------------------------------------------------------------------
 #: NamespaceProof.kind
@@ -1029,6 +1157,25 @@ class ExtendedDataSquare:
 
     def Roots(self) -> List[bytes]:
         return self.RowRoots() + self.ColRoots()
+
+    # --- data root (rsm_eds_data_root) ---
+    def DataRoot(self) -> bytes:
+        """The 32-byte data root: the RFC 6962 Merkle root over RowRoots() + ColRoots()
+        (DataAvailabilityHeader.Hash()).  A complete square with a device context hashes
+        its roots and the data root on the GPU; anything else runs the host trees."""
+        out = ctypes.create_string_buffer(32)
+        keep, fn, user = _tree_callback(self._tree_fn)
+        _check(library().rsm_eds_data_root(self._h, fn, user, out))
+        return out.raw
+
+    def RootProof(self, axis: int, index: int) -> "RootProof":
+        """The proof of RowRoots()[index] (``axis`` = Row) or ColRoots()[index] (Col) under
+        DataRoot() (rsm_data_root_prove over this square's roots)."""
+        L, w = library(), self.Width()
+        roots = self.Roots()
+        rec = ctypes.create_string_buffer(max(int(L.rsm_data_root_record_bytes(max(w, 1))), 1))
+        _check(L.rsm_data_root_prove(b"".join(roots), w, len(roots[0]) if roots else 0, axis, index, rec))
+        return _parse_root_records(rec.raw, [(axis, index)], w)[0]
 
     # --- Repair (extendeddatacrossword.go:74-84) ---
     def Repair(self, rowRoots: Sequence[bytes], colRoots: Sequence[bytes]) -> None:

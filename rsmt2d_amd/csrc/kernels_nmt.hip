@@ -23,7 +23,9 @@
 //                     lays its node message out in its own LDS bytes and hashes it.
 // Also nmt_nodes_kernel (every node kept: the proofs' node store) and
 // nmt_proof_verify_kernel (one lane per sampled share: leaf, fold of its proof through
-// hash_node, compare with the committed root; any width up to 65536) and
+// hash_node, compare with the committed root; any width up to 65536),
+// nmt_proof_verify_data_root_kernel (the same lane, hashing the fold's node as a leaf of
+// the data-root tree and folding on to the square's data root: no root table) and
 // nmt_ns_verify_kernel (one wave per namespace proof: the leaves of its range, the fold of
 // its range proof in the wave's LDS, the completeness checks; any width up to 1024).
 // Namespace sizes up to 32 bytes (Celestia: 29), widths up to 1024 (LDS permitting).
@@ -31,6 +33,7 @@
 #include <cstdint>
 #include <utility>
 
+#include "dataroot_dev.hpp"
 #include "rsm_kernels.hpp"
 #include "sha256_dev.hpp"
 
@@ -970,40 +973,19 @@ __device__ __forceinline__ void verify_leaf(const uint8_t* share, uint32_t S, ui
     for (int i = 0; i < 8; ++i) out.d[i] = h[i];
 }
 
+// The share's leaf node folded through the n_nodes derived siblings at `nodes` (NL bytes
+// each; bit i of mask: sibling i is the right operand) into acc; false where a fold step
+// has unordered siblings.  mb: the lane's LDS message bytes (NS == 0).
 template <int NS>
-__global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __restrict__ shares,
-                                                               const uint8_t* __restrict__ records,
-                                                               const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
-                                                               uint32_t ns, uint32_t k, uint32_t ignore_max,
-                                                               const ProofSample* __restrict__ samples, uint32_t n,
-                                                               uint32_t* __restrict__ status) {
-    extern __shared__ uint32_t lds[];  // NS == 0: the lanes' node messages
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= n) return;
-    const ProofSample sm = samples[t];
-    const uint32_t L = proof_levels(W), NL = 2u * ns + 32u;
-    const uint8_t* rec = records + (uint64_t)t * (8u + L * NL);
-    uint32_t n_nodes = 0, mask = 0;
-    for (uint32_t l = 0; l < L; ++l) {
-        const uint32_t j = sm.pos >> l;
-        if ((j ^ 1u) < proof_level_count(W, l)) {
-            if (!(j & 1u)) mask |= 1u << n_nodes;
-            ++n_nodes;
-        }
-    }
-    if (ld_any<uint32_t>(rec) != n_nodes || ld_any<uint32_t>(rec + 4) != mask) {
-        status[t] = kProofMalformed;
-        return;
-    }
-    const bool q0 = sm.index < k && sm.pos < k, ig = ignore_max != 0;
-    uint8_t* mb = reinterpret_cast<uint8_t*>(lds) + (NS == 0 ? threadIdx.x * (64u * node_blocks(ns)) : 0u);
-    Node acc;
-    if constexpr (NS == 29) verify_leaf29(shares + (uint64_t)t * S, S, q0, acc);
-    else verify_leaf(shares + (uint64_t)t * S, S, ns, q0, acc);
+__device__ __forceinline__ bool nmt_share_fold(const uint8_t* share, uint32_t S, const uint8_t* nodes, uint32_t n_nodes,
+                                               uint32_t mask, uint32_t ns, bool q0, bool ig, uint8_t* mb, Node& acc) {
+    const uint32_t NL = 2u * ns + 32u;
+    if constexpr (NS == 29) verify_leaf29(share, S, q0, acc);
+    else verify_leaf(share, S, ns, q0, acc);
     bool ordered = true;
     for (uint32_t i = 0; i < n_nodes; ++i) {
         Node nd, l, r, o;
-        node_from_bytes<NS>(rec + 8u + i * NL, ns, nd);
+        node_from_bytes<NS>(nodes + i * NL, ns, nd);
         const bool right = (mask >> i) & 1u;  // the sibling is the right operand
 #pragma unroll
         for (int q = 0; q < (int)kNsWords; ++q) {
@@ -1028,12 +1010,109 @@ __global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __
         }
         acc = o;
     }
+    return ordered;
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __restrict__ shares,
+                                                               const uint8_t* __restrict__ records,
+                                                               const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
+                                                               uint32_t ns, uint32_t k, uint32_t ignore_max,
+                                                               const ProofSample* __restrict__ samples, uint32_t n,
+                                                               uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // NS == 0: the lanes' node messages
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint32_t L = proof_levels(W), NL = 2u * ns + 32u;
+    const uint8_t* rec = records + (uint64_t)t * (8u + L * NL);
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(W, sm.pos, &mask);
+    if (ld_any<uint32_t>(rec) != n_nodes || ld_any<uint32_t>(rec + 4) != mask) {
+        status[t] = kProofMalformed;
+        return;
+    }
+    const bool q0 = sm.index < k && sm.pos < k, ig = ignore_max != 0;
+    uint8_t* mb = reinterpret_cast<uint8_t*>(lds) + (NS == 0 ? threadIdx.x * (64u * node_blocks(ns)) : 0u);
+    Node acc;
+    const bool ordered = nmt_share_fold<NS>(shares + (uint64_t)t * S, S, rec + 8u, n_nodes, mask, ns, q0, ig, mb, acc);
     Node rt;
     node_from_bytes<NS>(roots + (((uint64_t)sm.square * 2u + sm.axis) * W + sm.index) * NL, ns, rt);
     uint32_t diff = 0;
 #pragma unroll
     for (int q = 0; q < (int)kNsWords; ++q) diff |= (acc.mn[q] ^ rt.mn[q]) | (acc.mx[q] ^ rt.mx[q]) | (acc.d[q] ^ rt.d[q]);
     status[t] = !ordered ? kProofOrder : (diff ? kProofRoot : kProofOk);
+}
+
+// Chained verification (rsm_kernels.hpp "data root"), NMT: the same lane, with no root
+// table.  Both headers -- the share record's against (W, pos), the root record's against
+// (2W, axis W + index) -- are compared before anything is hashed.  The share fold's node
+// min || max || digest is the candidate root: its 2 ns + 32 bytes are hashed as leaf
+// axis W + index of the data-root tree (dataroot_dev.hpp), folded through the root
+// record's 32-byte digests and compared with the square's data root.  NS = 29: the
+// candidate's bytes come from compile-time positions; NS = 0: from the lane's LDS message
+// bytes (at least 128 for every namespace size), as hash_node lays out a node.
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_proof_verify_data_root_kernel(
+    const uint8_t* __restrict__ shares, const uint8_t* __restrict__ records, const uint8_t* __restrict__ root_records,
+    const uint8_t* __restrict__ data_roots, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+    const ProofSample* __restrict__ samples, uint32_t n, uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // NS == 0: the lanes' node messages
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint32_t NL = 2u * ns + 32u;
+    const uint8_t* rec = records + (uint64_t)t * (8u + proof_levels(W) * NL);
+    const uint8_t* rrec = root_records + (uint64_t)t * (8u + proof_levels(2u * W) * 32u);
+    uint32_t mask = 0, mask2 = 0;
+    const uint32_t n_nodes = proof_shape(W, sm.pos, &mask);
+    const uint32_t n2 = proof_shape(2u * W, sm.axis * W + sm.index, &mask2);
+    if (ld_any<uint32_t>(rec) != n_nodes || ld_any<uint32_t>(rec + 4) != mask || ld_any<uint32_t>(rrec) != n2 ||
+        ld_any<uint32_t>(rrec + 4) != mask2) {
+        status[t] = kProofMalformed;
+        return;
+    }
+    const bool q0 = sm.index < k && sm.pos < k, ig = ignore_max != 0;
+    uint8_t* mb = reinterpret_cast<uint8_t*>(lds) + (NS == 0 ? threadIdx.x * (64u * node_blocks(ns)) : 0u);
+    Node acc;
+    if (!nmt_share_fold<NS>(shares + (uint64_t)t * S, S, rec + 8u, n_nodes, mask, ns, q0, ig, mb, acc)) {
+        status[t] = kProofOrder;
+        return;
+    }
+    uint32_t B[kRootWords], g[8];  // the candidate root's bytes as big-endian words
+    if constexpr (NS == 0) {
+        uint32_t* mw = reinterpret_cast<uint32_t*>(mb);
+#pragma unroll
+        for (int i = 0; i < kRootWords; ++i) mw[i] = 0;
+#pragma unroll
+        for (int i = 0; i < (int)kMaxNs; ++i)
+            if (i < (int)ns) {
+                mb[i] = be_byte(acc.mn, i);
+                mb[(int)ns + i] = be_byte(acc.mx, i);
+            }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) mb[2 * (int)ns + i] = be_byte(acc.d, i);
+#pragma unroll
+        for (int i = 0; i < kRootWords; ++i) B[i] = __builtin_bswap32(mw[i]);
+    } else {
+        WNode<NS> x;
+#pragma unroll
+        for (int q = 0; q < (int)kNsWords; ++q) x.mn[q] = acc.mn[q], x.mx[q] = acc.mx[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x.d[q] = acc.d[q];
+        constexpr int NLc = 2 * NS + 32;
+        sfor_n<kRootWords>([&](auto Ic) {
+            constexpr int i = decltype(Ic)::value;
+            uint32_t v = 0;
+            if constexpr (4 * i < NLc) v |= node_byte<NS, 4 * i>(x) << 24;
+            if constexpr (4 * i + 1 < NLc) v |= node_byte<NS, 4 * i + 1>(x) << 16;
+            if constexpr (4 * i + 2 < NLc) v |= node_byte<NS, 4 * i + 2>(x) << 8;
+            if constexpr (4 * i + 3 < NLc) v |= node_byte<NS, 4 * i + 3>(x);
+            B[i] = v;
+        });
+    }
+    root_leaf_hash(B, NL, g);
+    status[t] = data_root_matches(g, rrec, n2, mask2, data_roots + (uint64_t)sm.square * 32u) ? kProofOk : kProofRoot;
 }
 
 // ---------------------------------------------------------------------------
@@ -1238,6 +1317,22 @@ hipError_t launch_nmt_proof_verify(const uint8_t* d_shares, const uint8_t* d_rec
     else
         hipLaunchKernelGGL(nmt_proof_verify_kernel<0>, grid, dim3(256), (size_t)256 * 64u * node_blocks(ns), st, d_shares,
                            d_records, d_roots, W, S, ns, k, ignore_max, d_samples, n, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmt_proof_verify_data_root(const uint8_t* d_shares, const uint8_t* d_records,
+                                             const uint8_t* d_root_records, const uint8_t* d_data_roots, uint32_t W,
+                                             uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+                                             const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + 255) / 256);
+    if (ns == 29 && S % 64 == 0 && S >= 64)
+        hipLaunchKernelGGL(nmt_proof_verify_data_root_kernel<29>, grid, dim3(256), 0, st, d_shares, d_records,
+                           d_root_records, d_data_roots, W, S, ns, k, ignore_max, d_samples, n, d_status);
+    else
+        hipLaunchKernelGGL(nmt_proof_verify_data_root_kernel<0>, grid, dim3(256), (size_t)256 * 64u * node_blocks(ns), st,
+                           d_shares, d_records, d_root_records, d_data_roots, W, S, ns, k, ignore_max, d_samples, n,
+                           d_status);
     return hipGetLastError();
 }
 

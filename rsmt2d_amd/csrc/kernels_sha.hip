@@ -14,37 +14,20 @@
 //                      (S/64 + 1 blocks); the digest of a cell serves both its row
 //                      tree and its column tree.
 //   tree_root_kernel : a few trees per wave (2W trees), levels in place in LDS.
-// Also tree_nodes_kernel (every node kept: the proofs' node store) and
+// Also tree_nodes_kernel (every node kept: the proofs' node store),
 // proof_verify_kernel (one lane per sampled share: leaf hash, fold of its proof, compare
-// with the committed root).
+// with the committed root) and proof_verify_data_root_kernel (the same lane, folding on
+// through the root's proof under the square's data root).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "dataroot_dev.hpp"
 #include "rsm_kernels.hpp"
 #include "sha256_dev.hpp"
 
 namespace rsm {
 
 namespace {
-
-// SHA256(0x01 || L || R) for digests held as 8 big-endian words each.
-__device__ __forceinline__ void node_hash(const uint32_t (&L)[8], const uint32_t (&R)[8], uint32_t (&out)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[i] = kH0[i];
-    uint32_t w[16];
-    w[0] = shift8(0x01u, L[0]);
-#pragma unroll
-    for (int i = 1; i < 8; ++i) w[i] = shift8(L[i - 1], L[i]);
-    w[8] = shift8(L[7], R[0]);
-#pragma unroll
-    for (int i = 1; i < 8; ++i) w[8 + i] = shift8(R[i - 1], R[i]);
-    sha_block(out, w);
-    w[0] = (R[7] << 24) | 0x00800000u;
-#pragma unroll
-    for (int i = 1; i < 15; ++i) w[i] = 0;
-    w[15] = 65u * 8u;
-    sha_block(out, w);
-}
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
@@ -364,35 +347,11 @@ __global__ __launch_bounds__(256) void tree_nodes_kernel(uint32_t* __restrict__ 
 // (two compressions each) and compares with its root: no intermediate buffer.  Records
 // sit at any alignment (memcpy loads: gfx950 global loads need none); nothing past the
 // derived nodes is read, and no address depends on what a record or a share holds.
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__global__ __launch_bounds__(256) void proof_verify_kernel(const uint8_t* __restrict__ shares,
-                                                           const uint8_t* __restrict__ records,
-                                                           const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
-                                                           const ProofSample* __restrict__ samples, uint32_t n,
-                                                           uint32_t* __restrict__ status) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= n) return;
-    const ProofSample sm = samples[t];
-    const uint32_t L = proof_levels(W);
-    const uint8_t* rec = records + (uint64_t)t * (8u + L * 32u);
-    uint32_t n_nodes = 0, mask = 0;
-    for (uint32_t l = 0; l < L; ++l) {
-        const uint32_t j = sm.pos >> l;
-        if ((j ^ 1u) < proof_level_count(W, l)) {
-            if (!(j & 1u)) mask |= 1u << n_nodes;
-            ++n_nodes;
-        }
-    }
-    if (ld_u32(rec) != n_nodes || ld_u32(rec + 4) != mask) {
-        status[t] = kProofMalformed;
-        return;
-    }
-    const v4u* p = reinterpret_cast<const v4u*>(shares + (uint64_t)t * S);
-    uint32_t h[8];
+// (proof_shape, fold_digests: dataroot_dev.hpp, shared with the chained kernels.)
+
+// the leaf digest of a share (S a multiple of 64, 16-byte aligned), as leaf_hash_kernel
+__device__ __forceinline__ void share_leaf_hash(const uint8_t* share, uint32_t S, uint32_t (&h)[8]) {
+    const v4u* p = reinterpret_cast<const v4u*>(share);
 #pragma unroll
     for (int i = 0; i < 8; ++i) h[i] = kH0[i];
     uint32_t prev = 0;  // the 0x00 leaf prefix
@@ -411,33 +370,69 @@ __global__ __launch_bounds__(256) void proof_verify_kernel(const uint8_t* __rest
         }
         sha_block(h, w);
     }
-    {
-        uint32_t w[16];
-        w[0] = (prev << 24) | 0x00800000u;
+    uint32_t w[16];
+    w[0] = (prev << 24) | 0x00800000u;
 #pragma unroll
-        for (int i = 1; i < 15; ++i) w[i] = 0;
-        w[15] = (S + 1u) * 8u;
-        sha_block(h, w);
+    for (int i = 1; i < 15; ++i) w[i] = 0;
+    w[15] = (S + 1u) * 8u;
+    sha_block(h, w);
+}
+
+__global__ __launch_bounds__(256) void proof_verify_kernel(const uint8_t* __restrict__ shares,
+                                                           const uint8_t* __restrict__ records,
+                                                           const uint8_t* __restrict__ roots, uint32_t W, uint32_t S,
+                                                           const ProofSample* __restrict__ samples, uint32_t n,
+                                                           uint32_t* __restrict__ status) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint8_t* rec = records + (uint64_t)t * (8u + proof_levels(W) * 32u);
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(W, sm.pos, &mask);
+    if (ld_u32(rec) != n_nodes || ld_u32(rec + 4) != mask) {
+        status[t] = kProofMalformed;
+        return;
     }
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        const uint8_t* nd = rec + 8u + i * 32u;
-        const bool right = (mask >> i) & 1u;  // the sibling is the right operand
-        uint32_t a[8], b[8], o[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint32_t x = __builtin_bswap32(ld_u32(nd + 4 * q));
-            a[q] = right ? h[q] : x;
-            b[q] = right ? x : h[q];
-        }
-        node_hash(a, b, o);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) h[q] = o[q];
-    }
+    uint32_t h[8];
+    share_leaf_hash(shares + (uint64_t)t * S, S, h);
+    fold_digests(h, rec + 8u, n_nodes, mask);
     const uint8_t* rt = roots + (((uint64_t)sm.square * 2u + sm.axis) * W + sm.index) * 32u;
     uint32_t diff = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) diff |= h[q] ^ __builtin_bswap32(ld_u32(rt + 4 * q));
     status[t] = diff ? kProofRoot : kProofOk;
+}
+
+// Chained verification (rsm_kernels.hpp "data root"), DefaultTree: the same lane, with no
+// root table.  Both headers -- the share record's against (W, pos), the root record's
+// against (2W, axis W + index) -- are compared before anything is hashed; the share fold's
+// digest is then hashed as leaf axis W + index of the data-root tree, folded through the
+// root record and compared with the square's data root.  Both records sit at any
+// alignment; nothing past either record's derived nodes is read.
+__global__ __launch_bounds__(256) void proof_verify_data_root_kernel(
+    const uint8_t* __restrict__ shares, const uint8_t* __restrict__ records, const uint8_t* __restrict__ root_records,
+    const uint8_t* __restrict__ data_roots, uint32_t W, uint32_t S, const ProofSample* __restrict__ samples, uint32_t n,
+    uint32_t* __restrict__ status) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    const ProofSample sm = samples[t];
+    const uint8_t* rec = records + (uint64_t)t * (8u + proof_levels(W) * 32u);
+    const uint8_t* rrec = root_records + (uint64_t)t * (8u + proof_levels(2u * W) * 32u);
+    uint32_t mask = 0, mask2 = 0;
+    const uint32_t n_nodes = proof_shape(W, sm.pos, &mask);
+    const uint32_t n2 = proof_shape(2u * W, sm.axis * W + sm.index, &mask2);
+    if (ld_u32(rec) != n_nodes || ld_u32(rec + 4) != mask || ld_u32(rrec) != n2 || ld_u32(rrec + 4) != mask2) {
+        status[t] = kProofMalformed;
+        return;
+    }
+    uint32_t h[8];
+    share_leaf_hash(shares + (uint64_t)t * S, S, h);
+    fold_digests(h, rec + 8u, n_nodes, mask);
+    uint32_t B[kRootWords], g[8];  // the candidate root: the digest itself
+#pragma unroll
+    for (int i = 0; i < kRootWords; ++i) B[i] = i < 8 ? h[i] : 0u;
+    root_leaf_hash(B, 32u, g);
+    status[t] = data_root_matches(g, rrec, n2, mask2, data_roots + (uint64_t)sm.square * 32u) ? kProofOk : kProofRoot;
 }
 
 }  // namespace
@@ -447,6 +442,15 @@ hipError_t launch_proof_verify(const uint8_t* d_shares, const uint8_t* d_records
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(proof_verify_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_shares, d_records, d_roots, W, S,
                        d_samples, n, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_proof_verify_data_root(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_root_records,
+                                         const uint8_t* d_data_roots, uint32_t W, uint32_t S,
+                                         const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(proof_verify_data_root_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_shares, d_records,
+                       d_root_records, d_data_roots, W, S, d_samples, n, d_status);
     return hipGetLastError();
 }
 

@@ -590,49 +590,38 @@ bool header_matches(const uint8_t* rec, uint32_t n_nodes, uint32_t mask) {
 
 }  // namespace
 
-extern "C" int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t n_leaves, uint32_t pos,
-                                       const uint8_t* record, const uint8_t* root, uint32_t* status) {
-    if ((!share && share_size) || !record || !root || !status || n_leaves == 0 || pos >= n_leaves) return RSM_EINVAL;
-    uint32_t mask = 0;
-    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
-    if (!header_matches(record, n_nodes, mask)) {
-        *status = RSM_PROOF_MALFORMED;
-        return RSM_OK;
-    }
-    Digest acc;
-    {
-        Sha256 s;
-        const uint8_t pre = 0x00;
-        s.update(&pre, 1);
-        s.update(share, share_size);
-        s.final(acc.b);
-    }
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        Digest nd;
-        memcpy(nd.b, record + 8 + (size_t)i * 32, 32);
-        acc = (mask >> i) & 1u ? node_hash(acc, nd) : node_hash(nd, acc);
-    }
-    *status = memcmp(acc.b, root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
-    return RSM_OK;
+namespace {
+
+// SHA256(0x00 || msg): a leaf of the DefaultTree and of the data-root tree
+Digest leaf_hash(const uint8_t* msg, size_t len) {
+    Sha256 s;
+    const uint8_t pre = 0x00;
+    s.update(&pre, 1);
+    s.update(msg, len);
+    Digest o;
+    s.final(o.b);
+    return o;
 }
 
-extern "C" int rsm_nmt_tree_verify(const rsm_nmt_params* p, uint32_t index, const uint8_t* share, uint32_t share_size,
-                                   uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root,
-                                   uint32_t* status) {
-    if (!p || !share || !record || !root || !status || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
-        pos >= n_leaves)
-        return RSM_EINVAL;
-    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32;
-    const bool ig = p->ignore_max_namespace != 0;
-    if (share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
-    uint32_t mask = 0;
-    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
-    if (!header_matches(record, n_nodes, mask)) {
-        *status = RSM_PROOF_MALFORMED;
-        return RSM_OK;
+// acc folded through n_nodes 32-byte siblings, bottom-up (bit i of mask: sibling i is the
+// right operand)
+void fold_digests(Digest& acc, const uint8_t* nodes, uint32_t n_nodes, uint32_t mask) {
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        Digest nd;
+        memcpy(nd.b, nodes + (size_t)i * 32, 32);
+        acc = (mask >> i) & 1u ? node_hash(acc, nd) : node_hash(nd, acc);
     }
-    std::vector<uint8_t> acc(NB), pair(2 * (size_t)NB), ns(nsz, 0xFF);
-    if (index < k && pos < k) memcpy(ns.data(), share, nsz);  // quadrant 0
+}
+
+// The NMT leaf node of `share` (quadrant 0: its own namespace, else 0xFF..) folded through
+// n_nodes siblings of 2 ns + 32 bytes into acc; false on unordered siblings.
+bool nmt_fold(const rsm_nmt_params* p, bool q0, const uint8_t* share, uint32_t share_size, const uint8_t* nodes,
+              uint32_t n_nodes, uint32_t mask, std::vector<uint8_t>& acc) {
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    std::vector<uint8_t> pair(2 * (size_t)NB), ns(nsz, 0xFF);
+    acc.assign(NB, 0);
+    if (q0) memcpy(ns.data(), share, nsz);
     memcpy(acc.data(), ns.data(), nsz);
     memcpy(acc.data() + nsz, ns.data(), nsz);
     {
@@ -644,21 +633,157 @@ extern "C" int rsm_nmt_tree_verify(const rsm_nmt_params* p, uint32_t index, cons
         s.final(acc.data() + 2 * nsz);
     }
     for (uint32_t i = 0; i < n_nodes; ++i) {
-        const uint8_t* nd = record + 8 + (size_t)i * NB;
+        const uint8_t* nd = nodes + (size_t)i * NB;
         const bool right = (mask >> i) & 1u;
         memcpy(pair.data(), right ? acc.data() : nd, NB);
         memcpy(pair.data() + NB, right ? nd : acc.data(), NB);
-        if (!nmt_pair(pair.data(), pair.data() + NB, nsz, ig, acc.data())) {
-            *status = RSM_PROOF_ORDER;
-            return RSM_OK;
-        }
+        if (!nmt_pair(pair.data(), pair.data() + NB, nsz, ig, acc.data())) return false;
         Sha256 s;
         const uint8_t pre = 0x01;
         s.update(&pre, 1);
         s.update(pair.data(), 2 * (size_t)NB);
         s.final(acc.data() + 2 * nsz);
     }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int rsm_default_tree_verify(const uint8_t* share, uint32_t share_size, uint32_t n_leaves, uint32_t pos,
+                                       const uint8_t* record, const uint8_t* root, uint32_t* status) {
+    if ((!share && share_size) || !record || !root || !status || n_leaves == 0 || pos >= n_leaves) return RSM_EINVAL;
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
+    if (!header_matches(record, n_nodes, mask)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    Digest acc = leaf_hash(share, share_size);
+    fold_digests(acc, record + 8, n_nodes, mask);
+    *status = memcmp(acc.b, root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_tree_verify(const rsm_nmt_params* p, uint32_t index, const uint8_t* share, uint32_t share_size,
+                                   uint32_t n_leaves, uint32_t pos, const uint8_t* record, const uint8_t* root,
+                                   uint32_t* status) {
+    if (!p || !share || !record || !root || !status || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
+        pos >= n_leaves)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32;
+    if (share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(n_leaves, pos, &mask);
+    if (!header_matches(record, n_nodes, mask)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    std::vector<uint8_t> acc;
+    if (!nmt_fold(p, index < k && pos < k, share, share_size, record + 8, n_nodes, mask, acc)) {
+        *status = RSM_PROOF_ORDER;
+        return RSM_OK;
+    }
     *status = memcmp(acc.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}
+
+// ---- data root (include/rsmt2d_hip.h "data root") ----
+// Host restatements of kernels_dataroot.hip and the chained verify kernels: the level
+// picture over the 2 * width roots, 32-byte digests at every level.
+namespace {
+
+// level 0 of the data-root tree: the leaf digests of the 2 * width roots
+std::vector<uint8_t> data_root_leaves(const uint8_t* roots, uint32_t width, uint32_t root_len) {
+    std::vector<uint8_t> lvl((size_t)2 * width * 32);
+    for (uint32_t t = 0; t < 2 * width; ++t) {
+        const Digest d = leaf_hash(roots + (size_t)t * root_len, root_len);
+        memcpy(&lvl[(size_t)t * 32], d.b, 32);
+    }
+    return lvl;
+}
+
+bool digest_join_pairs(const uint8_t* cur, uint32_t np, uint8_t* out) {
+    Digest dg[kHashBatch];
+    for (uint32_t j = 0; j < np; j += kHashBatch) {  // a pair is already the message body l || r
+        const int c = (int)std::min<uint32_t>(kHashBatch, np - j);
+        const uint8_t* m[kHashBatch];
+        for (int q = 0; q < c; ++q) m[q] = cur + (size_t)(j + q) * 64;
+        hash_prefixed(0x01, m, c, 64, dg);
+        for (int q = 0; q < c; ++q) memcpy(out + (size_t)(j + q) * 32, dg[q].b, 32);
+    }
+    return true;
+}
+
+bool data_root_args(const uint8_t* roots, uint32_t width, uint32_t root_len) {
+    return roots && width >= 1 && width <= (1u << 30) && root_len >= 1 && root_len <= 96;
+}
+
+}  // namespace
+
+extern "C" int rsm_data_root_prove(const uint8_t* roots, uint32_t width, uint32_t root_len, uint32_t axis, uint32_t index,
+                                   uint8_t* record_out) {
+    if (!data_root_args(roots, width, root_len) || !record_out || axis > 1 || index >= width) return RSM_EINVAL;
+    std::vector<uint8_t> lvl = data_root_leaves(roots, width, root_len);
+    prove_levels(lvl, 2 * width, 32, axis * width + index, record_out, digest_join_pairs);
+    return RSM_OK;
+}
+
+extern "C" int rsm_data_root(const uint8_t* roots, uint32_t width, uint32_t root_len, uint8_t* out) {
+    if (!data_root_args(roots, width, root_len) || !out) return RSM_EINVAL;
+    std::vector<uint8_t> lvl = data_root_leaves(roots, width, root_len);
+    std::vector<uint8_t> rec(8 + (size_t)proof_levels_of(2 * width) * 32);
+    prove_levels(lvl, 2 * width, 32, 0, rec.data(), digest_join_pairs);
+    memcpy(out, lvl.data(), 32);
+    return RSM_OK;
+}
+
+extern "C" int rsm_data_root_verify(const uint8_t* root_bytes, uint32_t root_len, uint32_t width, uint32_t axis,
+                                    uint32_t index, const uint8_t* record, const uint8_t* data_root, uint32_t* status) {
+    if (!data_root_args(root_bytes, width, root_len) || !record || !data_root || !status || axis > 1 || index >= width)
+        return RSM_EINVAL;
+    uint32_t mask = 0;
+    const uint32_t n_nodes = proof_shape(2 * width, axis * width + index, &mask);
+    if (!header_matches(record, n_nodes, mask)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    Digest acc = leaf_hash(root_bytes, root_len);
+    fold_digests(acc, record + 8, n_nodes, mask);
+    *status = memcmp(acc.b, data_root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}
+
+extern "C" int rsm_sample_verify_data_root(const rsm_nmt_params* nmt, uint32_t width, const rsm_sample* sm,
+                                           const uint8_t* share, uint32_t share_size, const uint8_t* record,
+                                           const uint8_t* root_record, const uint8_t* data_root, uint32_t* status) {
+    if (!sm || !share || !record || !root_record || !data_root || !status || width == 0 || width > (1u << 30) ||
+        sm->axis > 1 || sm->index >= width || sm->pos >= width)
+        return RSM_EINVAL;
+    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0)) return RSM_EINVAL;
+    if (nmt && share_size < nmt->namespace_size) return RSM_ETREE;  // data is too short to contain namespace ID
+    uint32_t mask = 0, mask2 = 0;
+    const uint32_t n_nodes = proof_shape(width, sm->pos, &mask);
+    const uint32_t n2 = proof_shape(2 * width, sm->axis * width + sm->index, &mask2);
+    if (!header_matches(record, n_nodes, mask) || !header_matches(root_record, n2, mask2)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    Digest acc;
+    if (nmt) {
+        std::vector<uint8_t> cand;
+        const uint32_t k = nmt->square_size;
+        if (!nmt_fold(nmt, sm->index < k && sm->pos < k, share, share_size, record + 8, n_nodes, mask, cand)) {
+            *status = RSM_PROOF_ORDER;
+            return RSM_OK;
+        }
+        acc = leaf_hash(cand.data(), cand.size());
+    } else {
+        Digest cand = leaf_hash(share, share_size);
+        fold_digests(cand, record + 8, n_nodes, mask);
+        acc = leaf_hash(cand.b, 32);
+    }
+    fold_digests(acc, root_record + 8, n2, mask2);
+    *status = memcmp(acc.b, data_root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
     return RSM_OK;
 }
 

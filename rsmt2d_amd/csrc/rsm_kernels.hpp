@@ -284,6 +284,44 @@ hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offs
                                 uint64_t shares_total, const uint8_t* d_roots, uint32_t W, uint32_t S, uint32_t ns,
                                 uint32_t k, uint32_t ignore_max, const NsQuery* d_queries, uint32_t n, uint32_t* d_status,
                                 hipStream_t st);
+// ---- data root (DESIGN.md §4 "Data root"; kernels_dataroot.hip) ----------------------
+// The tree over the N = 2W roots of a square (leaf t: the root bytes of tree t, rows then
+// columns, root_len = 32 .. 96 bytes each), in the level picture above with 32-byte
+// digests at every level: leaf SHA256(0x00 || root), node SHA256(0x01 || l || r), an
+// unpaired last node carried up.  Words of its node store, per square:
+//   [N][8]                     level 0: the leaf digests (big-endian words)
+//   [proof_tree_nodes(N)][8]   levels 1 .. L2 = proof_levels(N), level after level
+constexpr uint32_t kDataRootMaxWidth = 2048;  // every width for which device roots exist
+__host__ __device__ constexpr uint64_t data_root_tree_words(uint32_t W) {
+    return ((uint64_t)2 * W + proof_tree_nodes(2 * W)) * 8u;
+}
+// A root to prove: tree (axis, index) of square `square` (the C ABI's rsm_root_ref).
+struct RootRef {
+    uint32_t square, axis, index;
+};
+bool data_roots_dev_supported(uint32_t W);
+// One workgroup per square: d_roots [squares][2][W][root_len] (any alignment) ->
+// d_data_roots [squares][32] (any alignment); d_store (nullable, 16-byte aligned):
+// squares * data_root_tree_words(W) words.  LDS: W * 32 bytes.
+hipError_t launch_data_roots(const uint8_t* d_roots, uint32_t W, uint32_t root_len, uint32_t squares,
+                             uint8_t* d_data_roots, uint32_t* d_store, hipStream_t st);
+// n records of 8 + L2 * 32 bytes (any alignment) out of a store; refs validated on the host.
+hipError_t launch_data_root_gather(const uint32_t* d_store, uint32_t W, const RootRef* d_refs, uint32_t n,
+                                   uint8_t* d_records, hipStream_t st);
+// Chained verification (kernels_sha.hip, kernels_nmt.hip): launch_proof_verify /
+// launch_nmt_proof_verify with no root table.  Sample i also takes root record i
+// (d_root_records: [n][8 + L2 * 32], any alignment) and is compared with
+// d_data_roots[square] (32 bytes): the share fold's result is hashed as leaf
+// axis * W + index of the data-root tree and folded on.  Both headers are compared with
+// what (W, pos) and (2W, axis * W + index) dictate before anything is hashed
+// (kProofMalformed); then kProofOrder (NMT), kProofRoot, kProofOk.  Any 1 <= W <= 65536.
+hipError_t launch_proof_verify_data_root(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_root_records,
+                                         const uint8_t* d_data_roots, uint32_t W, uint32_t S,
+                                         const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st);
+hipError_t launch_nmt_proof_verify_data_root(const uint8_t* d_shares, const uint8_t* d_records,
+                                             const uint8_t* d_root_records, const uint8_t* d_data_roots, uint32_t W,
+                                             uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+                                             const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

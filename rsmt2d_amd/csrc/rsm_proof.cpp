@@ -5,8 +5,11 @@
 // rsm_proofs_verify_dev over the verify kernels (kernels_sha.hip, kernels_nmt.hip) and
 // rsm_eds_import_samples (verify, then SetCell); namespace proofs: rsm_ns_proofs_dev over
 // kernels_nsproof.hip, rsm_eds_namespace_proofs, and their receiving side
-// rsm_ns_proofs_verify_dev over nmt_ns_verify_kernel (kernels_nmt.hip).  Formats:
-// include/rsmt2d_hip.h.
+// rsm_ns_proofs_verify_dev over nmt_ns_verify_kernel (kernels_nmt.hip); the data root:
+// rsm_data_roots_dev and rsm_root_proofs_dev over kernels_dataroot.hip, and
+// rsm_proofs_verify_data_root_dev over the chained verify kernels, and rsm_eds_data_root
+// (the roots on the device as rsm_eds_roots computes them, then the data root there).
+// Formats: include/rsmt2d_hip.h.
 #include "eds_internal.hpp"
 
 #include <algorithm>
@@ -17,7 +20,9 @@ using namespace rsm;
 
 static_assert(sizeof(rsm_sample) == sizeof(ProofSample) && sizeof(rsm_sample) == 16, "rsm_sample is the kernels' sample");
 
-static_assert(sizeof(NsQuery) == 44 && kNsEmpty == RSM_NS_EMPTY && kNsInclusion == RSM_NS_INCLUSION &&
+static_assert(sizeof(rsm_root_ref) == sizeof(RootRef) && sizeof(rsm_root_ref) == 12, "rsm_root_ref is the kernels' ref");
+
+static_assert(sizeof(NsQuery) == 44&& kNsEmpty == RSM_NS_EMPTY && kNsInclusion == RSM_NS_INCLUSION &&
                   kNsAbsence == RSM_NS_ABSENCE && kNsTree == RSM_NS_TREE,
               "the kernels' namespace proof kinds are the C ABI's");
 
@@ -240,6 +245,144 @@ int rsm_proofs_verify_dev(rsm_ctx* ctx, const void* d_shares, const void* d_reco
                                       nmt->ignore_max_namespace, ds, n, static_cast<uint32_t*>(d_status), st)
             : launch_proof_verify(sh, rec, roots, width, share_size, ds, n, static_cast<uint32_t*>(d_status), st);
     return e == hipSuccess ? RSM_OK : hip_fail(e, "proof verify kernel launch");
+}
+
+uint32_t rsm_data_root_record_bytes(uint32_t width) { return width == 0 ? 0 : 8 + proof_levels(2 * width) * 32; }
+
+uint64_t rsm_data_root_nodes_bytes(uint32_t width, uint32_t count) {
+    if (!data_roots_dev_supported(width)) return 0;
+    return (uint64_t)count * data_root_tree_words(width) * 4;
+}
+
+int rsm_data_roots_dev(rsm_ctx* ctx, const void* d_roots, uint32_t width, uint32_t root_len, uint32_t count,
+                       void* d_data_roots, void* d_nodes, void* stream) {
+    if (!ctx || width == 0 || (count && (!d_roots || !d_data_roots)))
+        return fail(RSM_EINVAL, "rsm_data_roots_dev: bad arguments");
+    if (root_len < 32 || root_len > 96) return fail(RSM_EINVAL, "rsm_data_roots_dev: roots of %u bytes (32..96)", root_len);
+    if (reinterpret_cast<uintptr_t>(d_nodes) & 15u)
+        return fail(RSM_EINVAL, "rsm_data_roots_dev: d_nodes must be 16-byte aligned");
+    if (!data_roots_dev_supported(width))
+        return fail(RSM_EUNSUPPORTED, "rsm_data_roots_dev: width %u not supported (at most %u)", width, kDataRootMaxWidth);
+    if (count == 0) return RSM_OK;
+    if (int rc = use_device(ctx)) return rc;
+    const hipError_t e = launch_data_roots(static_cast<const uint8_t*>(d_roots), width, root_len, count,
+                                           static_cast<uint8_t*>(d_data_roots), static_cast<uint32_t*>(d_nodes),
+                                           pick(ctx, stream));
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "data root kernel launch");
+}
+
+int rsm_root_proofs_dev(rsm_ctx* ctx, const void* d_nodes, uint32_t width, uint32_t count, const rsm_root_ref* refs,
+                        uint32_t n, void* d_records, void* stream) {
+    if (!ctx || !d_nodes || width == 0 || (n && (!refs || !d_records)))
+        return fail(RSM_EINVAL, "rsm_root_proofs_dev: bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_nodes) & 15u)
+        return fail(RSM_EINVAL, "rsm_root_proofs_dev: d_nodes must be 16-byte aligned");
+    if (!data_roots_dev_supported(width))
+        return fail(RSM_EUNSUPPORTED, "rsm_root_proofs_dev: width %u not supported (at most %u)", width, kDataRootMaxWidth);
+    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_root_proofs_dev: at most %u refs per call", 1u << 24);
+    for (uint32_t i = 0; i < n; ++i)
+        if (refs[i].square >= count || refs[i].axis > 1 || refs[i].index >= width)
+            return fail(RSM_EINVAL, "rsm_root_proofs_dev: ref %u (square %u, axis %u, index %u) is out of range", i,
+                        refs[i].square, refs[i].axis, refs[i].index);
+    if (n == 0) return RSM_OK;
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const void* dr = nullptr;
+    if (int rc = stage_bytes(st, ss, refs, (size_t)n * sizeof(rsm_root_ref), &dr)) return rc;
+    const hipError_t e = launch_data_root_gather(static_cast<const uint32_t*>(d_nodes), width,
+                                                 static_cast<const RootRef*>(dr), n, static_cast<uint8_t*>(d_records), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "root proof gather kernel launch");
+}
+
+int rsm_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_shares, const void* d_records, const void* d_root_records,
+                                    const void* d_data_roots, uint32_t width, uint32_t share_size, uint32_t count,
+                                    const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n, void* d_status,
+                                    void* stream) {
+    if (!ctx || width == 0 || width > 65536u ||
+        (n && count && (!samples || !d_shares || !d_records || !d_root_records || !d_data_roots || !d_status)))
+        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: bad arguments");
+    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
+        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: namespace size %u (1..32) or square size 0",
+                    nmt->namespace_size);
+    if (reinterpret_cast<uintptr_t>(d_shares) & 15u)
+        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: d_shares must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_status) & 3u)
+        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: d_status must be 4-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: at most %u samples per call", 1u << 24);
+    if (n == 0 || count == 0) return RSM_OK;
+    const uint32_t bad = first_bad_sample(samples, n, count, width);
+    if (bad < n) return bad_sample("rsm_proofs_verify_data_root_dev", samples, bad);
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const ProofSample* ds = nullptr;
+    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
+    const auto* sh = static_cast<const uint8_t*>(d_shares);
+    const auto* rec = static_cast<const uint8_t*>(d_records);
+    const auto* rrec = static_cast<const uint8_t*>(d_root_records);
+    const auto* dr = static_cast<const uint8_t*>(d_data_roots);
+    const hipError_t e =
+        nmt ? launch_nmt_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, nmt->namespace_size, nmt->square_size,
+                                                nmt->ignore_max_namespace, ds, n, static_cast<uint32_t*>(d_status), st)
+            : launch_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, ds, n, static_cast<uint32_t*>(d_status), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "chained proof verify kernel launch");
+}
+
+int rsm_eds_data_root(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, uint8_t* out) {
+    if (!e || !out) return fail(RSM_EINVAL, "rsm_eds_data_root: bad arguments");
+    const uint32_t W = e->width, S = e->S;
+    if (W == 0) return fail(RSM_EINVAL, "rsm_eds_data_root: empty square");
+    DevTree dt;
+    const bool complete = memchr(e->present.data(), 0, e->present.size()) == nullptr;
+    // the condition under which rsm_eds_roots takes the device, and a width the build takes
+    if (e->ctx && complete && device_tree_for(tree_fn, user, W, &dt) && rsm_data_root_nodes_bytes(W, 1) != 0) {
+        rsm_ctx* ctx = e->ctx;
+        std::lock_guard<std::mutex> lk(ctx->eds_mu);
+        if (int rc = use_device(ctx)) return rc;
+        hipStream_t st = ctx->stream;
+        hipError_t r;
+        DevBuf& sq = ctx->eds.eds;
+        DevBuf& rb = ctx->eds.roots;
+        DevBuf& sb = ctx->eds.status;
+        // roots | the data root, in one buffer
+        const size_t o_dr = ((size_t)2 * W * dt.root_len + 15u) & ~(size_t)15u;
+        if ((r = sq.ensure(e->data.size())) != hipSuccess || (r = rb.ensure(o_dr + 32)) != hipSuccess ||
+            (r = sb.ensure((size_t)2 * W * 4)) != hipSuccess)
+            return hip_fail(r, "hipMalloc (data root)");
+        if ((r = hipMemcpyAsync(sq.ptr, e->data.data(), e->data.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
+            return hip_fail(r, "H2D square");
+        auto* d_roots = static_cast<uint8_t*>(rb.ptr);
+        if (int rc = device_tree_roots(ctx, dt, static_cast<const uint8_t*>(sq.ptr), W, S, d_roots,
+                                       static_cast<uint32_t*>(sb.ptr), st))
+            return rc;
+        if (int rc = rsm_data_roots_dev(ctx, d_roots, W, dt.root_len, 1, d_roots + o_dr, nullptr, st)) return rc;
+        std::vector<uint32_t> status((size_t)2 * W);
+        uint8_t got[32];
+        if ((r = hipMemcpyAsync(got, d_roots + o_dr, 32, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (r = hipMemcpyAsync(status.data(), sb.ptr, status.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(r, "D2H data root");
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(r, "data root stream");
+        for (uint32_t i = 0; i < 2 * W; ++i)
+            if (status[i]) return fail(RSM_ETREE, "tree error computing root %u (namespace push order)", i % W);
+        memcpy(out, got, 32);
+        return RSM_OK;
+    }
+    constexpr uint32_t kCap = 96;  // the longest root a data-root leaf takes
+    std::vector<uint8_t> wide((size_t)2 * W * kCap);
+    uint32_t len[2] = {0, 0};
+    for (int axis = 0; axis < 2; ++axis)
+        if (int rc = rsm_eds_roots(e, axis, tree_fn, user, wide.data() + (size_t)axis * W * kCap, kCap, &len[axis])) return rc;
+    if (len[0] != len[1] || len[0] == 0)
+        return fail(RSM_ETREE, "rsm_eds_data_root: row roots of %u bytes, column roots of %u", len[0], len[1]);
+    std::vector<uint8_t> roots((size_t)2 * W * len[0]);
+    for (uint32_t t = 0; t < 2 * W; ++t) memcpy(&roots[(size_t)t * len[0]], &wide[(size_t)t * kCap], len[0]);
+    if (int rc = rsm_data_root(roots.data(), W, len[0], out)) return fail(rc, "rsm_eds_data_root: bad roots");
+    return RSM_OK;
 }
 
 int rsm_eds_import_samples(rsm_eds* e, const uint8_t* row_roots, const uint8_t* col_roots, uint32_t root_len,

@@ -54,5 +54,31 @@ __device__ __forceinline__ void sha_block(uint32_t (&h)[8], uint32_t (&w)[16]) {
     h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
 }
 
+// SHA256(0x01 || L || R) for digests held as 8 big-endian words each.
+__device__ __forceinline__ void node_hash(const uint32_t (&L)[8], const uint32_t (&R)[8], uint32_t (&out)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] = kH0[i];
+    uint32_t w[16];
+    w[0] = shift8(0x01u, L[0]);
+#pragma unroll
+    for (int i = 1; i < 8; ++i) w[i] = shift8(L[i - 1], L[i]);
+    w[8] = shift8(L[7], R[0]);
+#pragma unroll
+    for (int i = 1; i < 8; ++i) w[8 + i] = shift8(R[i - 1], R[i]);
+    sha_block(out, w);
+    w[0] = (R[7] << 24) | 0x00800000u;
+#pragma unroll
+    for (int i = 1; i < 15; ++i) w[i] = 0;
+    w[15] = 65u * 8u;
+    sha_block(out, w);
+}
+
+// a 32-bit load at any alignment (memcpy: gfx950 global loads need none)
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
 }  // namespace
 }  // namespace rsm
