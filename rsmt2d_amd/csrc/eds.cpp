@@ -535,33 +535,20 @@ int fast_repair_rows_zero_copy(rsm_eds* e, DevSquare& dev, const std::vector<uin
         ds.grid = zc_grid;
         return launch_decode(dev.ctx, ds, st);
     };
-    // complete rows (not decoded) go up as they are, top half first
-    auto upload_complete = [&](uint32_t lo, uint32_t hi, size_t t) -> int {
-        for (uint32_t i = lo; i < hi;) {
-            if (t < todo.size() && todo[t] == i) {
-                ++i, ++t;
-                continue;
-            }
-            uint32_t j = i;
-            while (j < hi && !(t < todo.size() && todo[t] == j)) ++j;
-            if ((r = hipMemcpyAsync(dev.d_eds + i * row, e->data.data() + i * row, (j - i) * row,
-                                    hipMemcpyHostToDevice, st)) != hipSuccess)
-                return hip_fail(r, "H2D complete rows");
-            i = j;
-        }
-        return RSM_OK;
-    };
+    // Complete rows are not decoded and need no copy here: a square that has one went
+    // through the pre-repair check, which uploaded the WHOLE host square into dev.d_eds
+    // to verify its complete vectors (DevSquare::upload), and nothing has written there
+    // since (the caller holds eds_mu across both).  A device square missing such a row
+    // fails the encoding compare below (tests/test_gpu_repair_patterns.py, rows_uneven).
     const bool halves = repair_mode() == 1;  // (diagnostic A/B: the two-launch form)
     size_t split = todo.size();
     if (halves) {
         split = 0;
         while (split < todo.size() && todo[split] < k) ++split;
     }
-    if (int rc = upload_complete(0, halves ? k : W, 0)) return rc;
     if (int rc = sweep(0, split)) return rc;
     if (halves) {
         (void)hipEventRecord(ev_top, st);
-        if (int rc = upload_complete(k, W, split)) return rc;
         if (int rc = sweep(split, todo.size())) return rc;
     }
     (void)hipEventRecord(ev_bot, st);
