@@ -720,6 +720,87 @@ typedef struct {
 } rsm_repair_stats;
 int rsm_eds_repair_stats(const rsm_eds* eds, rsm_repair_stats* out);
 
+/* ---- Repair of device-resident squares ---------------------------------------------- */
+/* The last step of the sampling flow without the host square: samples verified by
+ * rsm_proofs_verify_dev are set into device squares (rsm_samples_scatter_dev), and the
+ * squares are repaired and checked where they lie, a batch per call
+ * (rsm_repair_squares_dev).  No share crosses the bus; between sweeps a few words per
+ * square do.  Status of a square: */
+#define RSM_REPAIR_OK 0        /* complete, a valid 2D codeword, every root the committed one */
+#define RSM_REPAIR_STUCK 1     /* the sweeps stopped with cells missing; nothing was verified */
+#define RSM_REPAIR_ENCODING 2  /* complete, but not the extension of its own Q0 */
+#define RSM_REPAIR_ROOTS 3     /* a valid codeword, but a root (or an NMT tree status) differs */
+typedef struct {
+    uint32_t status;          /* RSM_REPAIR_* */
+    uint32_t sweeps;          /* passes that decoded something in this square */
+    uint32_t decoded_vectors; /* rows and columns decoded by them */
+    uint32_t missing;         /* cells still missing (0 unless STUCK) */
+} rsm_repair_result;
+/* Bytes of the caller's scratch for one call (re-extension copies, leaf digests, roots,
+ * tree statuses, todo lists, flags: about count * (4 k^2 share_size + 4 k^2 * 32, NMT 64));
+ * 0 for shapes the call does not take. */
+uint64_t rsm_repair_work_bytes(uint32_t k, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt);
+/* Repairs `count` squares in place.  d_eds (device, 16-byte aligned) is
+ * [count][2k][2k][share_size] as in rsm_extend_squares_dev; d_presence (device, 16-byte
+ * aligned, in/out) [count][2k][2k] bytes, non-zero = the cell is given; d_roots (device,
+ * any alignment) the committed roots [count][2][2k][root_len] exactly as
+ * rsm_roots_squares_dev / rsm_nmt_roots_squares_dev write them (nmt == NULL: the
+ * DefaultTree, root_len 32; else 2 * namespace_size + 32); d_work (device, 16-byte
+ * aligned) rsm_repair_work_bytes of scratch; results (HOST) count records.  No other
+ * device memory is allocated per call (the codec's own grow-only per-stream scratch of
+ * the GF(2^16) decoders aside).
+ *
+ * Schedule: that of rsm_eds_repair's device fast path.  A row pass, then a column pass,
+ * and so on; a pass decodes every vector of its axis with k <= cells < 2k at once, in
+ * every square that has one, and counts as one sweep for such a square.  The lists come
+ * from a planner kernel over the presence bytes (ascending indices, so the result does
+ * not depend on scheduling); the host reads one count per square from pinned memory
+ * after each pass and launches the decoders.  A square drops out once it misses nothing
+ * or two passes in a row found nothing in it (it is stuck), while the others go on; the
+ * loop ends when every square has, after at most 4k decoding passes.
+ * Completed squares are then verified as one batch on the device: Q0 is copied to d_work
+ * and re-extended, and the square must equal the result (else RSM_REPAIR_ENCODING; this
+ * compare is consulted first, as in rsm_repair_stats); all 4k roots of every such square
+ * are computed and must equal d_roots, with every NMT tree status zero (else
+ * RSM_REPAIR_ROOTS).  Two flags per square return to the host.
+ *
+ * Contract.  A cell whose presence byte is non-zero on entry is never written.  On return
+ * d_presence holds the peeling closure: non-zero in every cell of a square that completed
+ * (given cells keep their byte unless a decoded vector crosses them, which sets 1), and in
+ * a STUCK square exactly in the given cells and the cells of decoded vectors.  In squares
+ * that are not OK the cells missing on entry hold unspecified bytes.  The call returns
+ * after everything it enqueued on `stream` (NULL: the context's) has completed.
+ * There is no pre-repair check of the given vectors and no attribution: RSM_REPAIR_OK
+ * means what acceptance by rsm_eds_repair's fast path means, and anything else names no
+ * vector.  A caller who needs ErrByzantineData{Axis, Index, Shares} takes the given cells
+ * to rsm_eds_repair, whose exact solver finds it.
+ * Limits: those of the device trees -- 2k <= 2048 for the DefaultTree, 2k <= 1024 with
+ * namespace_size 1..32 and 2k <= 2 * square_size for the NMT -- and count * 4 k^2 < 2^32,
+ * count <= 65535; beyond them RSM_EUNSUPPORTED (and rsm_repair_work_bytes is 0).
+ * RSM_ESHARESIZE for a share size that is no multiple of 64, RSM_EINVAL for k == 0, empty
+ * shares, NULL or misaligned operands, RSM_ETREE for shares shorter than the namespace.
+ * count == 0 launches nothing. */
+int rsm_repair_squares_dev(rsm_ctx* ctx, void* d_eds, void* d_presence, uint32_t k, uint32_t share_size,
+                           uint32_t count, const rsm_nmt_params* nmt, const void* d_roots, void* d_work,
+                           rsm_repair_result* results, void* stream);
+/* The apply step of rsm_eds_import_samples on device squares: d_eds / d_presence as above
+ * (d_presence any alignment here), `samples` HOST memory, validated and copied as in
+ * rsm_proofs_verify_dev (against `count` squares of width 2k; n <= 2^24), d_shares
+ * [n][share_size] (16-byte aligned) and d_status [n] uint32 as the verifier wrote them.
+ * A sample addresses cell (index, pos) for a row and (pos, index) for a column of its
+ * square.  With the statuses and presence bytes as they stand on entry: a status-0 sample
+ * on a nil cell, with no lower-indexed status-0 sample of the batch on the same cell, has
+ * its share copied in and the presence byte set to 1; every other status-0 sample (cell
+ * present on entry, or won by a lower index) gets RSM_PROOF_OCCUPIED in d_status and
+ * writes nothing else; any other status writes nothing.  These are the results of
+ * applying the samples in order, and they do not depend on the order lanes run in: a
+ * launch decides from the entry state, a second one applies.  Takes no caller scratch.
+ * Argument errors as rsm_repair_squares_dev (any 1 <= k <= 32768: no tree is built).
+ * n == 0 or count == 0 launches nothing.  Asynchronous on `stream`. */
+int rsm_samples_scatter_dev(rsm_ctx* ctx, void* d_eds, void* d_presence, uint32_t k, uint32_t share_size,
+                            uint32_t count, const rsm_sample* samples, uint32_t n, const void* d_shares,
+                            void* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ __all__ = [
     "RSM_PROOF_OK", "RSM_PROOF_MALFORMED", "RSM_PROOF_ORDER", "RSM_PROOF_ROOT", "RSM_PROOF_OCCUPIED",
     "RSM_PROOF_NAMESPACE", "RSM_PROOF_INCOMPLETE", "verify_namespaces_dev", "verify_namespace_data",
     "RootRef", "RootProof", "data_roots_dev", "prove_roots_dev", "verify_samples_data_root_dev",
+    "RepairResult", "repair_squares_dev", "scatter_samples_dev",
+    "REPAIR_OK", "REPAIR_STUCK", "REPAIR_ENCODING", "REPAIR_ROOTS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -119,6 +121,16 @@ class RepairStats(ctypes.Structure):
     """rsm_repair_stats (include/rsmt2d_hip.h): counters of the last Repair."""
     _fields_ =[("fast_path", ctypes.c_int32), ("sweeps", ctypes.c_uint32),
                 ("decoded_vectors", ctypes.c_uint32), ("fallback_reason", ctypes.c_uint32)]
+
+
+#: rsm_repair_result.status of rsm_repair_squares_dev (include/rsmt2d_hip.h)
+REPAIR_OK, REPAIR_STUCK, REPAIR_ENCODING, REPAIR_ROOTS = 0, 1, 2, 3
+
+
+class RepairResult(ctypes.Structure):
+    """rsm_repair_result (include/rsmt2d_hip.h): one square of rsm_repair_squares_dev."""
+    _fields_ = [("status", ctypes.c_uint32), ("sweeps", ctypes.c_uint32),
+                ("decoded_vectors", ctypes.c_uint32), ("missing", ctypes.c_uint32)]
 
 
 # (name, restype, argtypes) of every symbol declared in include/rsmt2d_hip.h
@@ -234,6 +246,10 @@ SIGNATURES = {
     "rsm_sample_verify_data_root": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _VP, _U32, _VP, _VP, _VP,
                                            ctypes.POINTER(_U32)]),
     "rsm_eds_data_root": (_I32, [_VP, _VP, _VP, _VP]),
+    "rsm_repair_work_bytes": (_U64, [_U32, _U32, _U32, ctypes.POINTER(NmtParams)]),
+    "rsm_repair_squares_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP,
+                                      ctypes.POINTER(RepairResult), _VP]),
+    "rsm_samples_scatter_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _VP]),
 }
 
 
@@ -749,6 +765,49 @@ def verify_samples_dev(shares: "DeviceBuffer", records: "DeviceBuffer", roots: "
     finally:
         st.free()
     return out
+
+
+def scatter_samples_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
+                        samples: Sequence[tuple], shares: "DeviceBuffer", status: "DeviceBuffer", count: int = 1):
+    """Sets the verified ones of ``(square, axis, index, pos)`` samples into ``count``
+    device-resident [2k][2k][share_size] squares (rsm_samples_scatter_dev): ``shares``
+    ([n][share_size]) and ``status`` ([n] uint32, as rsm_proofs_verify_dev wrote it) stay
+    on the device; a status-0 sample on a nil cell is copied in and its byte of
+    ``presence_buf`` ([count][2k][2k]) set, a status-0 sample on a present cell or behind
+    a lower-indexed one of the same cell becomes RSM_PROOF_OCCUPIED.  Returns the status
+    words afterwards."""
+    import numpy as np
+    L, ctx, n = library(), eds_buf.ctx, len(samples)
+    if n == 0:
+        return np.zeros(0, np.uint32)
+    arr = (Sample * n)(*[Sample(*s) for s in samples])
+    _check(L.rsm_samples_scatter_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, arr, n, shares.ptr,
+                                     status.ptr, None))
+    _check(L.rsm_sync(ctx))
+    return status.download(n * 4).view(np.uint32).copy()
+
+
+def repair_squares_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
+                       roots_buf: "DeviceBuffer", count: int = 1, nmt: Optional[NmtParams] = None) -> List[RepairResult]:
+    """Repairs ``count`` device-resident [2k][2k][share_size] squares in place
+    (rsm_repair_squares_dev).  ``presence_buf``: [count][2k][2k] bytes, non-zero = given,
+    on return the peeling closure; ``roots_buf``: the committed roots
+    [count][2][2k][root bytes] as rsm_roots_squares_dev / rsm_nmt_roots_squares_dev write
+    them.  One RepairResult per square: status (REPAIR_*), sweeps, decoded_vectors,
+    missing.  No attribution of a bad vector: that is Repair()'s on a host square."""
+    L, ctx = library(), eds_buf.ctx
+    p = ctypes.byref(nmt) if nmt is not None else None
+    nbytes = int(L.rsm_repair_work_bytes(k, share_size, count, p))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device repair: {count} squares of width {2 * k} not supported")
+    res = (RepairResult * max(count, 1))()
+    work = DeviceBuffer(nbytes)
+    try:
+        _check(L.rsm_repair_squares_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, p, roots_buf.ptr,
+                                        work.ptr, res, None))
+    finally:
+        work.free()
+    return list(res[:count])
 
 
 # ---------------------------------------------------------------------------

@@ -7,6 +7,13 @@
 
 #include "rsm_internal.hpp"
 
+namespace rsm {
+// Uploads `bytes` of a call's host arguments through the staging buffers of stream `st`
+// (rsm_proof.cpp; ss.mu held): *dev is the device copy, valid for kernels enqueued on
+// `st` before the next call on it.
+int stage_bytes(hipStream_t st, StreamScratch& ss, const void* src, size_t bytes, const void** dev);
+}  // namespace rsm
+
 // Host bytes of a square: pinned (hipHostMalloc) whenever a HIP runtime is
 // usable, so Repair's square upload and download are direct DMA; plain memory on
 // a host without a GPU (Import/New are host-only operations).

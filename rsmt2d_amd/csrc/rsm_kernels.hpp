@@ -322,6 +322,38 @@ hipError_t launch_nmt_proof_verify_data_root(const uint8_t* d_shares, const uint
                                              const uint8_t* d_root_records, const uint8_t* d_data_roots, uint32_t W,
                                              uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
                                              const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st);
+// ---- device-resident Repair (DESIGN.md §5 "Device-resident Repair"; kernels_repair.hip) ----
+// The sweep planner, one workgroup per square of d_presence ([count][W][W] bytes, 4-byte
+// aligned, non-zero = present; 2 <= W <= 2048, even).  A launch first marks present every
+// cell of the vectors its predecessor listed (d_prev_todo, of the other axis), then lists
+// in d_todo ([count][W]) the vectors of `axis` with k <= have < W, ascending.  d_state:
+// one word per square that belongs to the planner (its last todo count); first: it is
+// not read.  report (pinned host memory through its device mapping, or device memory):
+// per square the todo count and the cells missing before this pass's decodes.
+bool repair_plan_supported(uint32_t W);
+hipError_t launch_repair_plan(uint8_t* d_presence, uint32_t W, uint32_t count, uint32_t axis, bool first,
+                              const uint32_t* d_prev_todo, uint32_t* d_todo, uint32_t* d_state, uint32_t* report,
+                              hipStream_t st);
+// Batch verification of n completed squares, square d_map[j] of d_eds against work square
+// j (both [2k][2k][S], 16-byte aligned): the Q0 copy, then after the work squares are
+// re-extended d_flags[2j] = 1 where the squares differ, and d_flags[2j + 1] = 1 where the
+// roots computed for work square j (d_got: roots_bytes per square, any alignment) differ
+// from the committed ones of square d_map[j] or a tree status word (d_status: `words` per
+// square, nullable) is non-zero.  The flags start at 0.
+hipError_t launch_repair_gather_q0(const uint8_t* d_eds, uint8_t* d_work, const uint32_t* d_map, uint32_t k, uint32_t S,
+                                   uint32_t n, hipStream_t st);
+hipError_t launch_repair_compare_squares(const uint8_t* d_eds, const uint8_t* d_work, const uint32_t* d_map,
+                                         uint64_t sq_bytes, uint32_t n, uint32_t* d_flags, hipStream_t st);
+hipError_t launch_repair_compare_roots(const uint8_t* d_got, const uint32_t* d_status, const uint8_t* d_committed,
+                                       const uint32_t* d_map, uint32_t roots_bytes, uint32_t words, uint32_t n,
+                                       uint32_t* d_flags, hipStream_t st);
+// Verified samples into device squares, two launches: decide (one lane per sample, from
+// the statuses and the presence bytes as they stand; d_prev[i]: the next lower sample of
+// the same cell or ~0; d_verdict: n words of scratch), then apply (one wave per sample:
+// the winners' shares and presence bytes, kProofOccupied into the losers' status words).
+hipError_t launch_samples_scatter(const ProofSample* d_samples, const uint32_t* d_prev, uint32_t* d_verdict,
+                                  const uint8_t* d_shares, uint8_t* d_eds, uint8_t* d_presence, uint32_t* d_status,
+                                  uint32_t W, uint32_t S, uint32_t n, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

@@ -31,29 +31,7 @@ static_assert(kProofOk == RSM_PROOF_OK && kProofMalformed == RSM_PROOF_MALFORMED
                   kProofIncomplete == RSM_PROOF_INCOMPLETE,
               "the kernels' status words are the C ABI's");
 
-namespace {
-
-// The device tree of (width, nmt), or false beyond the root kernels' limits.
-bool proof_tree_for(uint32_t width, const rsm_nmt_params* nmt, DevTree* t) {
-    return device_tree_for(nmt ? rsm_nmt_tree_root : nullptr, const_cast<rsm_nmt_params*>(nmt), width, t);
-}
-
-uint64_t store_bytes(const DevTree& t, uint32_t W, uint32_t count) {
-    return 4 * (t.nmt ? proof_store_words(W, count, kProofNmtLeafWords, kProofNmtNodeWords)
-                      : proof_store_words(W, count, kProofShaWords, kProofShaWords));
-}
-
-// the first sample out of range, or n
-uint32_t first_bad_sample(const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width) {
-    for (uint32_t i = 0; i < n; ++i)
-        if (s[i].square >= count || s[i].axis > 1 || s[i].index >= width || s[i].pos >= width) return i;
-    return n;
-}
-
-int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
-    return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", who, i, s[i].square,
-                s[i].axis, s[i].index, s[i].pos);
-}
+namespace rsm {
 
 // Uploads `bytes` of a call's host arguments through the stream's staging buffers
 // (ss.mu held): *dev is the device copy, valid for kernels enqueued on `st` before the
@@ -78,6 +56,32 @@ int stage_bytes(hipStream_t st, StreamScratch& ss, const void* src, size_t bytes
     if ((e = hipEventRecord(ss.samp_ev, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
     *dev = ss.samp_dev.ptr;
     return RSM_OK;
+}
+
+}  // namespace rsm
+
+namespace {
+
+// The device tree of (width, nmt), or false beyond the root kernels' limits.
+bool proof_tree_for(uint32_t width, const rsm_nmt_params* nmt, DevTree* t) {
+    return device_tree_for(nmt ? rsm_nmt_tree_root : nullptr, const_cast<rsm_nmt_params*>(nmt), width, t);
+}
+
+uint64_t store_bytes(const DevTree& t, uint32_t W, uint32_t count) {
+    return 4 * (t.nmt ? proof_store_words(W, count, kProofNmtLeafWords, kProofNmtNodeWords)
+                      : proof_store_words(W, count, kProofShaWords, kProofShaWords));
+}
+
+// the first sample out of range, or n
+uint32_t first_bad_sample(const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (s[i].square >= count || s[i].axis > 1 || s[i].index >= width || s[i].pos >= width) return i;
+    return n;
+}
+
+int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
+    return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", who, i, s[i].square,
+                s[i].axis, s[i].index, s[i].pos);
 }
 
 int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
