@@ -770,10 +770,10 @@ uint64_t rsm_repair_work_bytes(uint32_t k, uint32_t share_size, uint32_t count, 
  * a STUCK square exactly in the given cells and the cells of decoded vectors.  In squares
  * that are not OK the cells missing on entry hold unspecified bytes.  The call returns
  * after everything it enqueued on `stream` (NULL: the context's) has completed.
- * There is no pre-repair check of the given vectors and no attribution: RSM_REPAIR_OK
+ * This call has no pre-repair check of the given vectors and no attribution: RSM_REPAIR_OK
  * means what acceptance by rsm_eds_repair's fast path means, and anything else names no
- * vector.  A caller who needs ErrByzantineData{Axis, Index, Shares} takes the given cells
- * to rsm_eds_repair, whose exact solver finds it.
+ * vector.  A caller who needs ErrByzantineData{Axis, Index, Shares} calls
+ * rsm_repair_squares_checked_dev (below) instead, which names the vector on the device.
  * Limits: those of the device trees -- 2k <= 2048 for the DefaultTree, 2k <= 1024 with
  * namespace_size 1..32 and 2k <= 2 * square_size for the NMT -- and count * 4 k^2 < 2^32,
  * count <= 65535; beyond them RSM_EUNSUPPORTED (and rsm_repair_work_bytes is 0).
@@ -783,6 +783,74 @@ uint64_t rsm_repair_work_bytes(uint32_t k, uint32_t share_size, uint32_t count, 
 int rsm_repair_squares_dev(rsm_ctx* ctx, void* d_eds, void* d_presence, uint32_t k, uint32_t share_size,
                            uint32_t count, const rsm_nmt_params* nmt, const void* d_roots, void* d_work,
                            rsm_repair_result* results, void* stream);
+/* ---- Repair of device-resident squares with attribution ------------------------------- */
+/* rsm_repair_squares_dev with rsmt2d's ErrByzantineData: the same decoding passes, and
+ * around them every row and column is checked -- once, in the round in which it first has
+ * all 2k cells -- against its committed root and its own encoding.  A vector is therefore
+ * only ever built from cells that were given or that lie in vectors which passed. */
+#define RSM_REPAIR_BYZANTINE 4 /* a complete vector failed its check: see rsm_repair_check */
+#define RSM_BYZ_ROOT 1         /* its root differs from the committed one */
+#define RSM_BYZ_ENCODING 2     /* root equal, but parity != encode(first half) */
+#define RSM_BYZ_TREE 3         /* NMT only: the tree's status word is non-zero (consulted first) */
+typedef struct {
+    uint32_t axis, index;     /* valid when status == RSM_REPAIR_BYZANTINE */
+    uint32_t round;           /* 0 = entry check, p = after the square's p-th decoding pass (its p-th sweep) */
+    uint32_t reason;          /* RSM_BYZ_* ; 0 otherwise */
+    uint32_t checked_vectors; /* vectors whose root and encoding were evaluated */
+    uint32_t hashed_cells;    /* leaf records computed */
+} rsm_repair_check;
+/* Bytes of the checked call's scratch (one leaf record per cell, 32 bytes, NMT 64; one
+ * square for re-encoded parity; lists, verdict words, a bit and two bytes of bookkeeping
+ * per cell and vector); 0 exactly where rsm_repair_work_bytes is. */
+uint64_t rsm_repair_checked_work_bytes(uint32_t k, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt);
+/* Operands, alignment, limits and argument errors are those of rsm_repair_squares_dev
+ * (d_work: rsm_repair_checked_work_bytes); `checks` (HOST) receives count records and must
+ * not be NULL.
+ *
+ * Schedule.  The decoding passes are exactly those of rsm_repair_squares_dev (results[]:
+ * the same sweeps, decoded_vectors and missing for a square no check fails in).  Round 0
+ * checks the vectors complete on entry and names, among failures, the lowest (index, axis),
+ * row i before column i -- rsm_eds_repair's pre-repair order.  After a square's p-th
+ * decoding pass, of axis a, round p has two stages: stage 1 checks the vectors the pass
+ * decoded and names the lowest failing index; only if it is clean, stage 2 checks the
+ * vectors of the other axis that the pass completed and names the lowest failing index
+ * (after a stage-1 failure those hold cells of the failed vector, so naming one would be
+ * unsound).  A check evaluates, in this order, the NMT tree's status (RSM_BYZ_TREE), the
+ * root against d_roots (RSM_BYZ_ROOT) and the parity against a re-encode of the first
+ * half (RSM_BYZ_ENCODING).  The named vector is a minimum over keys computed on the
+ * device: no result depends on the order lanes run in.  A cell's leaf record is computed
+ * once per call (hashed_cells), every tree of a stage in one launch for the whole batch.
+ *
+ * A square with a failing vector is RSM_REPAIR_BYZANTINE and drops out at once, while
+ * the others go on.  After a failure in round 0 or in a stage 1 its d_presence stays as
+ * the failing pass's plan found it: that pass's decoded vectors are not marked.  After a
+ * failure in a stage 2 the pass's decoded vectors, which all passed stage 1, are marked,
+ * so the named vector is complete.  Either way every non-zero presence byte is a cell that
+ * was given or lies in a vector that passed its check, the named vector has at least k
+ * such cells, and decoding them gives a vector that fails the check: rsm_vectors_gather_dev
+ * of it yields ErrByzantineData.Shares, missing as nil, enough for a fraud proof.  (The
+ * reference's sequential solver returns an orthogonal vector without the rebuilt share,
+ * which can leave fewer than k.)  missing
+ * counts the zero presence bytes.  RSM_REPAIR_OK: nothing is missing and no check failed;
+ * every row and column was checked (checked_vectors == 4k, hashed_cells == 4k^2), so
+ * there is no whole-square verification afterwards.  RSM_REPAIR_STUCK as in
+ * rsm_repair_squares_dev, with no complete vector having failed.  RSM_REPAIR_ENCODING and
+ * RSM_REPAIR_ROOTS do not occur.  When several vectors are bad the one named may differ
+ * from rsm_eds_repair's sequential solver's; it always fails the check stated above on
+ * the shares rsm_vectors_gather_dev returns. */
+int rsm_repair_squares_checked_dev(rsm_ctx* ctx, void* d_eds, void* d_presence, uint32_t k, uint32_t share_size,
+                                   uint32_t count, const rsm_nmt_params* nmt, const void* d_roots, void* d_work,
+                                   rsm_repair_result* results, rsm_repair_check* checks, void* stream);
+/* Packs n vectors of device squares: refs (HOST; square < count, axis, index < 2k, else
+ * RSM_EINVAL; n <= 2^24) name them, d_shares (device, 16-byte aligned) receives
+ * [n][2k][share_size] and d_present (device) [n][2k] bytes copied from d_presence: the
+ * shares of ErrByzantineData, nil where the byte is 0 (those cells' bytes are whatever
+ * the square holds).  d_eds 16-byte aligned; any 1 <= k <= 32768; RSM_ESHARESIZE,
+ * RSM_EINVAL as in rsm_samples_scatter_dev; n == 0 or count == 0 launches nothing.
+ * Asynchronous on `stream`. */
+int rsm_vectors_gather_dev(rsm_ctx* ctx, const void* d_eds, const void* d_presence, uint32_t k, uint32_t share_size,
+                           uint32_t count, const rsm_root_ref* refs, uint32_t n, void* d_shares, void* d_present,
+                           void* stream);
 /* The apply step of rsm_eds_import_samples on device squares: d_eds / d_presence as above
  * (d_presence any alignment here), `samples` HOST memory, validated and copied as in
  * rsm_proofs_verify_dev (against `count` squares of width 2k; n <= 2^24), d_shares

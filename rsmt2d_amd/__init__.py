@@ -39,6 +39,8 @@ __all__ = [
     "RootRef", "RootProof", "data_roots_dev", "prove_roots_dev", "verify_samples_data_root_dev",
     "RepairResult", "repair_squares_dev", "scatter_samples_dev",
     "REPAIR_OK", "REPAIR_STUCK", "REPAIR_ENCODING", "REPAIR_ROOTS",
+    "REPAIR_BYZANTINE", "BYZ_ROOT", "BYZ_ENCODING", "BYZ_TREE", "RepairCheck", "repair_squares_checked_dev",
+    "gather_vectors_dev", "byzantine_data_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -131,6 +133,18 @@ class RepairResult(ctypes.Structure):
     """rsm_repair_result (include/rsmt2d_hip.h): one square of rsm_repair_squares_dev."""
     _fields_ = [("status", ctypes.c_uint32), ("sweeps", ctypes.c_uint32),
                 ("decoded_vectors", ctypes.c_uint32), ("missing", ctypes.c_uint32)]
+
+
+#: rsm_repair_squares_checked_dev: the status of a square with a bad vector, and
+#: rsm_repair_check.reason
+REPAIR_BYZANTINE = 4
+BYZ_ROOT, BYZ_ENCODING, BYZ_TREE = 1, 2, 3
+
+
+class RepairCheck(ctypes.Structure):
+    """rsm_repair_check (include/rsmt2d_hip.h): one square of rsm_repair_squares_checked_dev."""
+    _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("round", ctypes.c_uint32),
+                ("reason", ctypes.c_uint32), ("checked_vectors", ctypes.c_uint32), ("hashed_cells", ctypes.c_uint32)]
 
 
 # (name, restype, argtypes) of every symbol declared in include/rsmt2d_hip.h
@@ -249,6 +263,10 @@ SIGNATURES = {
     "rsm_repair_work_bytes": (_U64, [_U32, _U32, _U32, ctypes.POINTER(NmtParams)]),
     "rsm_repair_squares_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP,
                                       ctypes.POINTER(RepairResult), _VP]),
+    "rsm_repair_checked_work_bytes": (_U64, [_U32, _U32, _U32, ctypes.POINTER(NmtParams)]),
+    "rsm_repair_squares_checked_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP,
+                                              ctypes.POINTER(RepairResult), ctypes.POINTER(RepairCheck), _VP]),
+    "rsm_vectors_gather_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _VP]),
     "rsm_samples_scatter_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _VP]),
 }
 
@@ -794,7 +812,7 @@ def repair_squares_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k:
     on return the peeling closure; ``roots_buf``: the committed roots
     [count][2][2k][root bytes] as rsm_roots_squares_dev / rsm_nmt_roots_squares_dev write
     them.  One RepairResult per square: status (REPAIR_*), sweeps, decoded_vectors,
-    missing.  No attribution of a bad vector: that is Repair()'s on a host square."""
+    missing.  No attribution of a bad vector: that is ``repair_squares_checked_dev``'s."""
     L, ctx = library(), eds_buf.ctx
     p = ctypes.byref(nmt) if nmt is not None else None
     nbytes = int(L.rsm_repair_work_bytes(k, share_size, count, p))
@@ -808,6 +826,68 @@ def repair_squares_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k:
     finally:
         work.free()
     return list(res[:count])
+
+
+def repair_squares_checked_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
+                               roots_buf: "DeviceBuffer", count: int = 1, nmt: Optional[NmtParams] = None):
+    """``repair_squares_dev`` with attribution (rsm_repair_squares_checked_dev): the same
+    decoding passes, and every row and column is checked against its committed root and its
+    own encoding in the round in which it first has all 2k cells.  Returns one
+    ``(RepairResult, RepairCheck)`` per square.  A square with a bad vector has status
+    ``REPAIR_BYZANTINE``; its check names ``axis``, ``index``, ``round`` and ``reason``
+    (``BYZ_*``), and its presence bytes are non-zero only in cells that were given or lie
+    in vectors that passed: ``byzantine_data_dev`` turns that into ``ErrByzantineData``."""
+    L, ctx = library(), eds_buf.ctx
+    p = ctypes.byref(nmt) if nmt is not None else None
+    nbytes = int(L.rsm_repair_checked_work_bytes(k, share_size, count, p))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device repair: {count} squares of width {2 * k} not supported")
+    res = (RepairResult * max(count, 1))()
+    chk = (RepairCheck * max(count, 1))()
+    work = DeviceBuffer(nbytes)
+    try:
+        _check(L.rsm_repair_squares_checked_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, p,
+                                                roots_buf.ptr, work.ptr, res, chk, None))
+    finally:
+        work.free()
+    return list(zip(res[:count], chk[:count]))
+
+
+def gather_vectors_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
+                       refs: Sequence[tuple], count: int = 1):
+    """The ``(square, axis, index)`` vectors of device squares, packed and downloaded
+    (rsm_vectors_gather_dev): ``(shares [n][2k][share_size], present [n][2k])`` uint8."""
+    import numpy as np
+    L, ctx, n, W = library(), eds_buf.ctx, len(refs), 2 * k
+    if n == 0:
+        return np.zeros((0, W, share_size), np.uint8), np.zeros((0, W), np.uint8)
+    arr = (RootRef * n)(*[RootRef(*r) for r in refs])
+    shares, present = DeviceBuffer(n * W * share_size), DeviceBuffer(max(n * W, 16))
+    try:
+        _check(L.rsm_vectors_gather_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, arr, n, shares.ptr,
+                                        present.ptr, None))
+        _check(L.rsm_sync(ctx))
+        return (shares.download(n * W * share_size).reshape(n, W, share_size).copy(),
+                present.download(max(n * W, 16))[:n * W].reshape(n, W).copy())
+    finally:
+        shares.free()
+        present.free()
+
+
+def byzantine_data_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
+                       outcome: Sequence[tuple], count: int = 1) -> List[Optional[ErrByzantineData]]:
+    """``outcome``: what ``repair_squares_checked_dev`` returned for the same buffers.  One
+    entry per square: ``ErrByzantineData(Axis, Index, Shares)`` of a ``REPAIR_BYZANTINE``
+    square -- the named vector's shares prior to repair, ``None`` where missing -- else
+    ``None``.  One gather and one download for the batch."""
+    bad = [s for s in range(count) if outcome[s][0].status == REPAIR_BYZANTINE]
+    shares, present = gather_vectors_dev(eds_buf, presence_buf, k, share_size,
+                                         [(s, outcome[s][1].axis, outcome[s][1].index) for s in bad], count)
+    out: List[Optional[ErrByzantineData]] = [None] * count
+    for j, s in enumerate(bad):
+        out[s] = ErrByzantineData(int(outcome[s][1].axis), int(outcome[s][1].index),
+                                  [shares[j, p].tobytes() if present[j, p] else None for p in range(2 * k)])
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -287,13 +287,28 @@ __device__ __forceinline__ void lds_store(uint32_t* p, const Node& n) {
 // One workgroup per tree (blockIdx.x < W: row tree, else column tree; blockIdx.y the
 // square of a batch).  Dynamic LDS: two levels of W/2 nodes (ping-pong) + 256
 // per-thread message buffers.
+// LIST (checked Repair; rsm_kernels.hpp): the tree is entry blockIdx.x of the square's
+// lists instead, and its root is not stored but compared with the committed one
+// (`committed`: [squares][2][W][2 ns + 32] bytes): the entry's word of `verdict` receives
+// kByzTree where the tree fails, else kByzRoot where the roots differ, else 0.
+template <bool LIST>
 __global__ __launch_bounds__(256) void nmt_tree_kernel(const uint32_t* __restrict__ leaf, uint32_t W, uint32_t ns,
                                                        uint32_t ignore_max, uint8_t* __restrict__ roots,
-                                                       uint32_t* __restrict__ status) {
+                                                       uint32_t* __restrict__ status, const uint32_t* __restrict__ list,
+                                                       const uint32_t* __restrict__ list_cnt,
+                                                       const uint8_t* __restrict__ committed,
+                                                       uint32_t* __restrict__ verdict) {
     extern __shared__ uint32_t lds[];
+    uint32_t l_axis = 0, l_index = 0;
+    uint64_t l_slot = 0;
+    if constexpr (LIST) {  // the whole workgroup, before any barrier
+        if (!list_entry(list, list_cnt, W, blockIdx.y, blockIdx.x, &l_axis, &l_index, &l_slot)) return;
+    }
     leaf += (uint64_t)blockIdx.y * W * W * kLeafWords;
-    roots += (uint64_t)blockIdx.y * 2 * W * (2 * ns + 32);
-    if (status) status += (uint64_t)blockIdx.y * 2 * W;
+    if constexpr (!LIST) {
+        roots += (uint64_t)blockIdx.y * 2 * W * (2 * ns + 32);
+        if (status) status += (uint64_t)blockIdx.y * 2 * W;
+    }
     const uint32_t half = W / 2;
     auto lvl = [&](uint32_t which) -> uint32_t* { return lds + (size_t)which * half * kNodeWords; };
     // the spare node: lanes past a level's last node store their repeat there (below)
@@ -302,7 +317,7 @@ __global__ __launch_bounds__(256) void nmt_tree_kernel(const uint32_t* __restric
     __shared__ uint32_t bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
-    const uint32_t tree = blockIdx.x;
+    const uint32_t tree = LIST ? l_axis * W + l_index : blockIdx.x;
     const uint32_t axis = tree >= W ? 1u : 0u;
     const uint32_t idx = tree - axis * W;
     auto cell_of = [&](uint32_t pos) -> uint64_t { return axis == 0 ? (uint64_t)idx * W + pos : (uint64_t)pos * W + idx; };
@@ -368,6 +383,21 @@ __global__ __launch_bounds__(256) void nmt_tree_kernel(const uint32_t* __restric
     }
     if (my_bad) atomicOr(&bad, 1u);
     __syncthreads();
+    if (LIST) {
+        if (threadIdx.x == 0) {
+            Node rt;
+            lds_node(lvl(cur), rt);
+            const uint8_t* c = committed + ((uint64_t)blockIdx.y * 2 * W + tree) * (2 * ns + 32);
+            uint32_t diff = 0;
+#pragma unroll
+            for (int i = 0; i < (int)kMaxNs; ++i)
+                if (i < (int)ns) diff |= (uint32_t)(be_byte(rt.mn, i) ^ c[i]) | (uint32_t)(be_byte(rt.mx, i) ^ c[ns + i]);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) diff |= (uint32_t)(be_byte(rt.d, i) ^ c[2 * ns + i]);
+            verdict[l_slot] = bad ? kByzTree : (diff ? kByzRoot : 0u);
+        }
+        return;
+    }
     if (threadIdx.x == 0) {
         Node rt;
         lds_node(lvl(cur), rt);
@@ -1013,6 +1043,39 @@ __device__ __forceinline__ bool nmt_share_fold(const uint8_t* share, uint32_t S,
     return ordered;
 }
 
+// Leaf records of the listed vectors' cells that have none yet (checked Repair;
+// rsm_kernels.hpp): one lane per (entry, position) of square blockIdx.y.  The lane that
+// sets the cell's bit in `recorded` computes its record, as nmt_leaf29_kernel (NS = 29)
+// or nmt_leaf_kernel would; hashed[s] += the records computed (one add per wave).
+template <int NS>
+__global__ __launch_bounds__(256) void nmt_list_leaf_kernel(const uint8_t* __restrict__ eds, uint32_t W, uint32_t S,
+                                                            uint32_t ns, uint32_t k, const uint32_t* __restrict__ list,
+                                                            const uint32_t* __restrict__ cnt, uint32_t* recorded,
+                                                            uint32_t* hashed, uint32_t* __restrict__ leaf) {
+    const uint32_t s = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t e = i / W, pos = i - e * W;
+    uint32_t axis, index;
+    uint64_t slot;
+    if (!list_entry(list, cnt, W, s, e, &axis, &index, &slot)) return;
+    const uint32_t r = axis == 0 ? index : pos, c = axis == 0 ? pos : index;
+    const uint32_t cell = r * W + c;
+    const uint32_t bit = 1u << (cell & 31u);
+    const bool fresh = !(atomicOr(&recorded[(uint64_t)s * ((W * W + 31u) / 32u) + (cell >> 5)], bit) & bit);
+    if (fresh) {
+        Node n;
+        const uint8_t* share = eds + ((uint64_t)s * W * W + cell) * S;
+        if constexpr (NS == 29) verify_leaf29(share, S, r < k && c < k, n);
+        else verify_leaf(share, S, ns, r < k && c < k, n);
+        uint32_t* o = leaf + ((uint64_t)s * W * W + cell) * kLeafWords;
+#pragma unroll
+        for (int q = 0; q < (int)kNsWords; ++q) o[q] = n.mn[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[kNsWords + q] = n.d[q];
+    }
+    const uint64_t b = __ballot(fresh);
+    if (b && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(b)) atomicAdd(&hashed[s], (uint32_t)__popcll(b));
+}
+
 template <int NS>
 __global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __restrict__ shares,
                                                                const uint8_t* __restrict__ records,
@@ -1414,8 +1477,33 @@ hipError_t launch_nmt_roots(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32
     if (ns == 29 && (size_t)kNmtTreesPerBlock * wwave_lds_words<29>(W, 1, W % 4 == 0) * 4u <= kLdsCap)
         return launch_nmt_tree_wave<29>(d_leaf, W, ignore_max, d_roots, d_status, squares, st);
     const size_t lds = tree_lds_bytes(W, ns);
-    hipLaunchKernelGGL(nmt_tree_kernel, dim3(2 * W, squares), dim3(256), lds, st, d_leaf, W, ns, ignore_max, d_roots,
-                       d_status);
+    hipLaunchKernelGGL(nmt_tree_kernel<false>, dim3(2 * W, squares), dim3(256), lds, st, d_leaf, W, ns, ignore_max, d_roots,
+                       d_status, nullptr, nullptr, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+// ---- list-driven forms (checked Repair; rsm_kernels.hpp) ------------------------------
+hipError_t launch_nmt_list_leaves(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t count,
+                                  uint32_t max_n, const uint32_t* d_list, const uint32_t* d_cnt, uint32_t* d_recorded,
+                                  uint32_t* d_hashed, uint32_t* d_leaf, hipStream_t st) {
+    if (count == 0 || max_n == 0) return hipSuccess;
+    const dim3 grid((max_n * W + 255) / 256, count);
+    if (ns == 29 && S % 64 == 0 && S >= 64 && (reinterpret_cast<uintptr_t>(d_eds) & 15u) == 0)
+        hipLaunchKernelGGL(nmt_list_leaf_kernel<29>, grid, dim3(256), 0, st, d_eds, W, S, ns, k, d_list, d_cnt, d_recorded,
+                           d_hashed, d_leaf);
+    else
+        hipLaunchKernelGGL(nmt_list_leaf_kernel<0>, grid, dim3(256), 0, st, d_eds, W, S, ns, k, d_list, d_cnt, d_recorded,
+                           d_hashed, d_leaf);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmt_list_tree_check(const uint32_t* d_leaf, uint32_t W, uint32_t ns, uint32_t ignore_max,
+                                      uint32_t count, uint32_t max_n, const uint32_t* d_list, const uint32_t* d_cnt,
+                                      const uint8_t* d_committed, uint32_t* d_verdict, hipStream_t st) {
+    if (count == 0 || max_n == 0) return hipSuccess;
+    if (!nmt_dev_supported(W, ns)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmt_tree_kernel<true>, dim3(max_n, count), dim3(256), tree_lds_bytes(W, ns), st, d_leaf, W, ns,
+                       ignore_max, nullptr, nullptr, d_list, d_cnt, d_committed, d_verdict);
     return hipGetLastError();
 }
 

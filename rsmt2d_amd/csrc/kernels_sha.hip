@@ -504,4 +504,126 @@ hipError_t launch_tree_roots(const uint32_t* d_leaf, uint32_t W, uint32_t first,
     return launch_tree_kernel(d_leaf, W, d_roots, first, count, 1, true, st);
 }
 
+// ---- list-driven forms (checked Repair; rsm_kernels.hpp) ------------------------------
+namespace {
+
+// One lane per (entry, position) of square blockIdx.y.  The lane that sets the cell's bit
+// in `recorded` hashes the cell; hashed[s] += the records computed (one add per wave).
+__global__ __launch_bounds__(256) void list_leaf_hash_kernel(const uint8_t* __restrict__ eds, uint32_t W, uint32_t S,
+                                                             const uint32_t* __restrict__ list,
+                                                             const uint32_t* __restrict__ cnt, uint32_t* recorded,
+                                                             uint32_t* hashed, uint32_t* __restrict__ leaf) {
+    const uint32_t s = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t e = i / W, pos = i - e * W;
+    uint32_t axis, index;
+    uint64_t slot;
+    if (!list_entry(list, cnt, W, s, e, &axis, &index, &slot)) return;
+    const uint32_t cell = axis == 0 ? index * W + pos : pos * W + index;
+    const uint32_t bit = 1u << (cell & 31u);
+    const bool fresh = !(atomicOr(&recorded[(uint64_t)s * ((W * W + 31u) / 32u) + (cell >> 5)], bit) & bit);
+    if (fresh) {
+        uint32_t h[8];
+        share_leaf_hash(eds + ((uint64_t)s * W * W + cell) * S, S, h);
+        v4u* o = reinterpret_cast<v4u*>(leaf + ((uint64_t)s * W * W + cell) * 8u);
+        o[0] = v4u{h[0], h[1], h[2], h[3]};
+        o[1] = v4u{h[4], h[5], h[6], h[7]};
+    }
+    const uint64_t b = __ballot(fresh);
+    if (b && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(b)) atomicAdd(&hashed[s], (uint32_t)__popcll(b));
+}
+
+// One tree per wave (entry blockIdx.x * 4 + wave of square blockIdx.y), by levels in the
+// wave's own LDS (ceil(W / 2) digests): node (l, j) over leaves [j 2^l, min((j + 1) 2^l,
+// W)), an unpaired last node carried up unchanged -- tree_nodes_kernel's picture, the same
+// tree as tree_root_kernel's stack of subtrees.  A level is built in place (node j reads
+// 2j and 2j + 1 >= j; a 64-node pass reads before it writes, later passes read beyond
+// what it wrote), level 1 from the records.  Lane 0 compares the root with the committed
+// one.
+__global__ __launch_bounds__(256) void list_tree_check_kernel(const uint32_t* __restrict__ leaf, uint32_t W,
+                                                              const uint32_t* __restrict__ list,
+                                                              const uint32_t* __restrict__ cnt,
+                                                              const uint8_t* __restrict__ committed,
+                                                              uint32_t* __restrict__ verdict) {
+    extern __shared__ uint32_t lds_raw[];
+    const uint32_t s = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint32_t axis, index;
+    uint64_t slot;
+    if (!list_entry(list, cnt, W, s, blockIdx.x * 4u + wv, &axis, &index, &slot)) return;  // the whole wave
+    uint32_t* const lv = lds_raw + (size_t)wv * ((W + 1) / 2) * 8u;
+    leaf += (uint64_t)s * W * W * 8u;
+    auto leaf_at = [&](uint32_t pos, uint32_t (&d)[8]) {
+        const uint64_t cell = axis == 0 ? (uint64_t)index * W + pos : (uint64_t)pos * W + index;
+        const v4u* p = reinterpret_cast<const v4u*>(leaf + cell * 8u);
+        const v4u a = p[0], b = p[1];
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+    };
+    uint32_t prev = W;
+    for (uint32_t l = 1; prev > 1; ++l) {
+        const uint32_t n = (prev + 1) / 2;
+        for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
+            const uint32_t j = j0 + lane;
+            uint32_t a[8], b[8], o[8];
+            const bool act = j < n, pair = 2 * j + 1 < prev;
+            if (act) {
+                if (l == 1) {
+                    leaf_at(2 * j, a);
+                    if (pair) leaf_at(2 * j + 1, b);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        a[q] = lv[(2 * j) * 8u + q];
+                        b[q] = pair ? lv[(2 * j + 1) * 8u + q] : 0u;
+                    }
+                }
+                if (pair) {
+                    node_hash(a, b, o);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) o[q] = a[q];
+                }
+            }
+            // every read of this pass precedes its in-place writes
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (act) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) lv[j * 8u + q] = o[q];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        prev = n;
+    }
+    if (lane == 0) {
+        const uint8_t* rt = committed + (((uint64_t)s * 2u + axis) * W + index) * 32u;
+        uint32_t diff = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) diff |= lv[q] ^ __builtin_bswap32(ld_u32(rt + 4 * q));
+        verdict[slot] = diff ? kByzRoot : 0u;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_list_leaf_hashes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t count, uint32_t max_n,
+                                   const uint32_t* d_list, const uint32_t* d_cnt, uint32_t* d_recorded,
+                                   uint32_t* d_hashed, uint32_t* d_leaf, hipStream_t st) {
+    if (count == 0 || max_n == 0) return hipSuccess;
+    hipLaunchKernelGGL(list_leaf_hash_kernel, dim3((max_n * W + 255) / 256, count), dim3(256), 0, st, d_eds, W, S, d_list,
+                       d_cnt, d_recorded, d_hashed, d_leaf);
+    return hipGetLastError();
+}
+
+hipError_t launch_list_tree_check(const uint32_t* d_leaf, uint32_t W, uint32_t count, uint32_t max_n,
+                                  const uint32_t* d_list, const uint32_t* d_cnt, const uint8_t* d_committed,
+                                  uint32_t* d_verdict, hipStream_t st) {
+    if (count == 0 || max_n == 0) return hipSuccess;
+    if (!roots_dev_supported(W)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)4 * ((W + 1) / 2) * 8u * 4u;  // W = 2048: 128 KiB
+    hipLaunchKernelGGL(list_tree_check_kernel, dim3((max_n + 3) / 4, count), dim3(256), lds, st, d_leaf, W, d_list, d_cnt,
+                       d_committed, d_verdict);
+    return hipGetLastError();
+}
+
 }  // namespace rsm

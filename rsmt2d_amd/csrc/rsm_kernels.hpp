@@ -329,11 +329,13 @@ hipError_t launch_nmt_proof_verify_data_root(const uint8_t* d_shares, const uint
 // in d_todo ([count][W]) the vectors of `axis` with k <= have < W, ascending.  d_state:
 // one word per square that belongs to the planner (its last todo count); first: it is
 // not read.  report (pinned host memory through its device mapping, or device memory):
-// per square the todo count and the cells missing before this pass's decodes.
+// per square the todo count and the cells missing before this pass's decodes.  d_skip
+// (nullable): one word per square, non-zero = the square has dropped out of a checked
+// call; its presence bytes are left alone and it reports an empty list.
 bool repair_plan_supported(uint32_t W);
 hipError_t launch_repair_plan(uint8_t* d_presence, uint32_t W, uint32_t count, uint32_t axis, bool first,
                               const uint32_t* d_prev_todo, uint32_t* d_todo, uint32_t* d_state, uint32_t* report,
-                              hipStream_t st);
+                              hipStream_t st, const uint32_t* d_skip = nullptr);
 // Batch verification of n completed squares, square d_map[j] of d_eds against work square
 // j (both [2k][2k][S], 16-byte aligned): the Q0 copy, then after the work squares are
 // re-extended d_flags[2j] = 1 where the squares differ, and d_flags[2j + 1] = 1 where the
@@ -347,6 +349,70 @@ hipError_t launch_repair_compare_squares(const uint8_t* d_eds, const uint8_t* d_
 hipError_t launch_repair_compare_roots(const uint8_t* d_got, const uint32_t* d_status, const uint8_t* d_committed,
                                        const uint32_t* d_map, uint32_t roots_bytes, uint32_t words, uint32_t n,
                                        uint32_t* d_flags, hipStream_t st);
+// ---- checked Repair (rsm_repair_squares_checked_dev): every vector is checked against its
+// committed root and its own encoding in the stage in which it first has all W cells ----
+// A stage's lists (kernels_repair.hip): d_list [count][2][W] words (rows, then columns,
+// ascending), d_cnt [count][2], d_checked [count][2][W] bytes (zeroed by the caller once;
+// a listed vector's byte becomes 1).  mode 0: every complete vector, from d_presence
+// alone; 1: the vectors d_todo lists for `axis` (d_state: their count, as
+// launch_repair_plan left both); 2: the unchecked vectors of the other axis that are
+// complete once the cells of d_todo's vectors count as present.  A square with a non-zero
+// d_skip word lists nothing.  report (pinned, mapped): three words per square -- the two
+// counts and (mode 0) the cells missing.
+hipError_t launch_repair_check_plan(const uint8_t* d_presence, uint32_t W, uint32_t count, uint32_t mode, uint32_t axis,
+                                    const uint32_t* d_todo, const uint32_t* d_state, const uint32_t* d_skip,
+                                    uint8_t* d_checked, uint32_t* d_list, uint32_t* d_cnt, uint32_t* report,
+                                    hipStream_t st);
+// Leaf records of the listed vectors' cells that have none yet (kernels_sha.hip: 8 words
+// per cell; kernels_nmt.hip: 16, the node store's level 0), one lane per (list entry,
+// position) of grid (ceil(max_n W / 256), count); max_n: the largest cnt[s][0] + cnt[s][1].
+// d_recorded: one bit per cell, [count][ceil(W W / 32)] words, zeroed by the caller once
+// -- the lane that sets a cell's bit hashes it, so a cell is hashed once per call whichever
+// lane that is; d_hashed [count]: records computed so far (sums: no order shows in them).
+hipError_t launch_list_leaf_hashes(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t count, uint32_t max_n,
+                                   const uint32_t* d_list, const uint32_t* d_cnt, uint32_t* d_recorded,
+                                   uint32_t* d_hashed, uint32_t* d_leaf, hipStream_t st);
+hipError_t launch_nmt_list_leaves(const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t count,
+                                  uint32_t max_n, const uint32_t* d_list, const uint32_t* d_cnt, uint32_t* d_recorded,
+                                  uint32_t* d_hashed, uint32_t* d_leaf, hipStream_t st);
+// One tree per list entry over the records (leaves along the row, or strided down the
+// column), compared in the kernel with its committed root (d_committed: [count][2][W]
+// [root_len], any alignment): d_verdict, laid out as d_list, receives 0, kByzRoot or
+// (NMT, consulted first) kByzTree.  One launch for every square of the batch.
+constexpr uint32_t kByzRoot = 1, kByzEncoding = 2, kByzTree = 3;
+// Entry e of square s's lists: the rows first (cnt[s][0] of them), then the columns;
+// *slot: its word in d_list, d_verdict and the parity flags.  False past the last entry.
+__host__ __device__ inline bool list_entry(const uint32_t* list, const uint32_t* cnt, uint32_t W, uint32_t s, uint32_t e,
+                                           uint32_t* axis, uint32_t* index, uint64_t* slot) {
+    const uint32_t n0 = cnt[2 * s], n1 = cnt[2 * s + 1];
+    if (e >= n0 + n1) return false;
+    *axis = e >= n0 ? 1u : 0u;
+    *slot = (uint64_t)s * 2 * W + *axis * W + (e - *axis * n0);
+    *index = list[*slot];
+    return true;
+}
+hipError_t launch_list_tree_check(const uint32_t* d_leaf, uint32_t W, uint32_t count, uint32_t max_n,
+                                  const uint32_t* d_list, const uint32_t* d_cnt, const uint8_t* d_committed,
+                                  uint32_t* d_verdict, hipStream_t st);
+hipError_t launch_nmt_list_tree_check(const uint32_t* d_leaf, uint32_t W, uint32_t ns, uint32_t ignore_max,
+                                      uint32_t count, uint32_t max_n, const uint32_t* d_list, const uint32_t* d_cnt,
+                                      const uint8_t* d_committed, uint32_t* d_verdict, hipStream_t st);
+// A stage's verdict per square: the minimum over its failing list entries of
+// (2 index + axis) << 2 | reason (d_verdict's word, else kByzEncoding where d_parity's
+// word -- laid out as d_list -- is set), ~0 when none fails, into report[2 s] (pinned,
+// mapped); a failing square's d_skip word becomes 1.  stage2 (the lists are what a pass
+// of `axis` completed; d_todo, d_state as its plan left them): a failing square's decoded
+// vectors, which all passed stage 1, are marked present in d_presence -- no later plan
+// will -- and report[2 s + 1] counts the cells that were missing among them.
+hipError_t launch_repair_check_pick(const uint32_t* d_list, const uint32_t* d_cnt, const uint32_t* d_verdict,
+                                    const uint32_t* d_parity, uint32_t W, uint32_t count, bool stage2, uint32_t axis,
+                                    const uint32_t* d_todo, const uint32_t* d_state, uint8_t* d_presence,
+                                    uint32_t* d_skip, uint32_t* report, hipStream_t st);
+// d_shares [n][W][S] (16-byte aligned) and d_present [n][W]: vector d_refs[i] of the squares
+// and its presence bytes; refs validated on the host.
+hipError_t launch_vectors_gather(const uint8_t* d_eds, const uint8_t* d_presence, uint32_t W, uint32_t S,
+                                 const RootRef* d_refs, uint32_t n, uint8_t* d_shares, uint8_t* d_present,
+                                 hipStream_t st);
 // Verified samples into device squares, two launches: decide (one lane per sample, from
 // the statuses and the presence bytes as they stand; d_prev[i]: the next lower sample of
 // the same cell or ~0; d_verdict: n words of scratch), then apply (one wave per sample:
