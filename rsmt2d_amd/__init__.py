@@ -664,6 +664,17 @@ class Sample(ctypes.Structure):
                 ("pos", ctypes.c_uint32)]
 
 
+def _nmt_ref(nmt: Optional[NmtParams]):
+    """The ``const rsm_nmt_params*`` argument: NULL for the DefaultTree."""
+    return ctypes.byref(nmt) if nmt is not None else None
+
+
+def _records(kind, items: Sequence[tuple]):
+    """A ctypes array of ``kind`` (Sample, RootRef, NsQuery) from field tuples; one spare
+    element when there are none."""
+    return (kind * max(len(items), 1))(*[kind(*x) for x in items])
+
+
 class Proof:
     """A share with its Merkle proof in a row or column tree.
 
@@ -743,15 +754,14 @@ def prove_samples_dev(buf: "DeviceBuffer", width: int, share_size: int, samples:
     """Proofs of ``(square, axis, index, pos)`` samples of ``count`` complete
     device-resident [width][width][share_size] squares in ``buf``: one node-store
     build (rsm_proof_nodes_dev), one gather (rsm_proofs_dev)."""
-    L, ctx, n = library(), buf.ctx, len(samples)
-    p = ctypes.byref(nmt) if nmt is not None else None
+    L, ctx, n, p = library(), buf.ctx, len(samples), _nmt_ref(nmt)
     nbytes = int(L.rsm_proof_nodes_bytes(width, p, count))
     if nbytes == 0:
         raise RSMError(RSM_EUNSUPPORTED, f"device proofs: {count} squares of width {width} not supported")
     rb = int(L.rsm_proof_record_bytes(width, p))
     nodes, recs, shs = DeviceBuffer(nbytes), DeviceBuffer(max(n * rb, 16)), DeviceBuffer(max(n * share_size, 16))
     try:
-        arr = (Sample * max(n, 1))(*[Sample(*s) for s in samples])
+        arr = _records(Sample, samples)
         _check(L.rsm_proof_nodes_dev(ctx, buf.ptr, width, share_size, count, p, nodes.ptr, None, None, None))
         _check(L.rsm_proofs_dev(ctx, nodes.ptr, buf.ptr, width, share_size, count, p, arr, n, recs.ptr, shs.ptr, None))
         _check(L.rsm_sync(ctx))
@@ -775,9 +785,8 @@ def verify_samples_dev(shares: "DeviceBuffer", records: "DeviceBuffer", roots: "
         return out
     st = DeviceBuffer(n * 4)
     try:
-        arr = (Sample * n)(*[Sample(*s) for s in samples])
-        _check(L.rsm_proofs_verify_dev(ctx, shares.ptr, records.ptr, roots.ptr, width, share_size, count,
-                                       ctypes.byref(nmt) if nmt is not None else None, arr, n, st.ptr, None))
+        _check(L.rsm_proofs_verify_dev(ctx, shares.ptr, records.ptr, roots.ptr, width, share_size, count, _nmt_ref(nmt),
+                                       _records(Sample, samples), n, st.ptr, None))
         _check(L.rsm_sync(ctx))
         out[:] = st.download(n * 4).view(np.uint32)
     finally:
@@ -798,11 +807,27 @@ def scatter_samples_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k
     L, ctx, n = library(), eds_buf.ctx, len(samples)
     if n == 0:
         return np.zeros(0, np.uint32)
-    arr = (Sample * n)(*[Sample(*s) for s in samples])
-    _check(L.rsm_samples_scatter_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, arr, n, shares.ptr,
-                                     status.ptr, None))
+    _check(L.rsm_samples_scatter_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, _records(Sample, samples), n,
+                                     shares.ptr, status.ptr, None))
     _check(L.rsm_sync(ctx))
     return status.download(n * 4).view(np.uint32).copy()
+
+
+def _repair_squares(checked: bool, eds_buf, presence_buf, k, share_size, roots_buf, count, nmt):
+    """Both device Repair calls: the scratch sized and freed around the call; the result
+    records, with ``checked`` also the check records."""
+    L, ctx, p = library(), eds_buf.ctx, _nmt_ref(nmt)
+    nbytes = int((L.rsm_repair_checked_work_bytes if checked else L.rsm_repair_work_bytes)(k, share_size, count, p))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device repair: {count} squares of width {2 * k} not supported")
+    res, chk = (RepairResult * max(count, 1))(), (RepairCheck * max(count, 1))()
+    work = DeviceBuffer(nbytes)
+    try:
+        args = (ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, p, roots_buf.ptr, work.ptr, res)
+        _check(L.rsm_repair_squares_checked_dev(*args, chk, None) if checked else L.rsm_repair_squares_dev(*args, None))
+    finally:
+        work.free()
+    return list(res[:count]), list(chk[:count])
 
 
 def repair_squares_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
@@ -813,19 +838,7 @@ def repair_squares_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k:
     [count][2][2k][root bytes] as rsm_roots_squares_dev / rsm_nmt_roots_squares_dev write
     them.  One RepairResult per square: status (REPAIR_*), sweeps, decoded_vectors,
     missing.  No attribution of a bad vector: that is ``repair_squares_checked_dev``'s."""
-    L, ctx = library(), eds_buf.ctx
-    p = ctypes.byref(nmt) if nmt is not None else None
-    nbytes = int(L.rsm_repair_work_bytes(k, share_size, count, p))
-    if nbytes == 0:
-        raise RSMError(RSM_EUNSUPPORTED, f"device repair: {count} squares of width {2 * k} not supported")
-    res = (RepairResult * max(count, 1))()
-    work = DeviceBuffer(nbytes)
-    try:
-        _check(L.rsm_repair_squares_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, p, roots_buf.ptr,
-                                        work.ptr, res, None))
-    finally:
-        work.free()
-    return list(res[:count])
+    return _repair_squares(False, eds_buf, presence_buf, k, share_size, roots_buf, count, nmt)[0]
 
 
 def repair_squares_checked_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
@@ -837,20 +850,7 @@ def repair_squares_checked_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuf
     ``REPAIR_BYZANTINE``; its check names ``axis``, ``index``, ``round`` and ``reason``
     (``BYZ_*``), and its presence bytes are non-zero only in cells that were given or lie
     in vectors that passed: ``byzantine_data_dev`` turns that into ``ErrByzantineData``."""
-    L, ctx = library(), eds_buf.ctx
-    p = ctypes.byref(nmt) if nmt is not None else None
-    nbytes = int(L.rsm_repair_checked_work_bytes(k, share_size, count, p))
-    if nbytes == 0:
-        raise RSMError(RSM_EUNSUPPORTED, f"device repair: {count} squares of width {2 * k} not supported")
-    res = (RepairResult * max(count, 1))()
-    chk = (RepairCheck * max(count, 1))()
-    work = DeviceBuffer(nbytes)
-    try:
-        _check(L.rsm_repair_squares_checked_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, p,
-                                                roots_buf.ptr, work.ptr, res, chk, None))
-    finally:
-        work.free()
-    return list(zip(res[:count], chk[:count]))
+    return list(zip(*_repair_squares(True, eds_buf, presence_buf, k, share_size, roots_buf, count, nmt)))
 
 
 def gather_vectors_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k: int, share_size: int,
@@ -861,11 +861,10 @@ def gather_vectors_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k:
     L, ctx, n, W = library(), eds_buf.ctx, len(refs), 2 * k
     if n == 0:
         return np.zeros((0, W, share_size), np.uint8), np.zeros((0, W), np.uint8)
-    arr = (RootRef * n)(*[RootRef(*r) for r in refs])
     shares, present = DeviceBuffer(n * W * share_size), DeviceBuffer(max(n * W, 16))
     try:
-        _check(L.rsm_vectors_gather_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, arr, n, shares.ptr,
-                                        present.ptr, None))
+        _check(L.rsm_vectors_gather_dev(ctx, eds_buf.ptr, presence_buf.ptr, k, share_size, count, _records(RootRef, refs), n,
+                                        shares.ptr, present.ptr, None))
         _check(L.rsm_sync(ctx))
         return (shares.download(n * W * share_size).reshape(n, W, share_size).copy(),
                 present.download(max(n * W, 16))[:n * W].reshape(n, W).copy())
@@ -971,8 +970,7 @@ def prove_roots_dev(nodes: "DeviceBuffer", width: int, refs: Sequence[tuple], co
     rb = int(L.rsm_data_root_record_bytes(width))
     recs = DeviceBuffer(max(n * rb, 16))
     try:
-        arr = (RootRef * max(n, 1))(*[RootRef(*r) for r in refs])
-        _check(L.rsm_root_proofs_dev(ctx, nodes.ptr, width, count, arr, n, recs.ptr, None))
+        _check(L.rsm_root_proofs_dev(ctx, nodes.ptr, width, count, _records(RootRef, refs), n, recs.ptr, None))
         _check(L.rsm_sync(ctx))
         rec = recs.download(max(n * rb, 16)).tobytes()
     finally:
@@ -994,10 +992,9 @@ def verify_samples_data_root_dev(shares: "DeviceBuffer", records: "DeviceBuffer"
         return out
     st = DeviceBuffer(n * 4)
     try:
-        arr = (Sample * n)(*[Sample(*s) for s in samples])
         _check(L.rsm_proofs_verify_data_root_dev(ctx, shares.ptr, records.ptr, root_records.ptr, data_roots.ptr, width,
-                                                 share_size, count, ctypes.byref(nmt) if nmt is not None else None, arr,
-                                                 n, st.ptr, None))
+                                                 share_size, count, _nmt_ref(nmt), _records(Sample, samples), n, st.ptr,
+                                                 None))
         _check(L.rsm_sync(ctx))
         out[:] = st.download(n * 4).view(np.uint32)
     finally:
@@ -1101,7 +1098,7 @@ def prove_namespaces_dev(buf: "DeviceBuffer", width: int, share_size: int, queri
     bufs = [DeviceBuffer(nbytes), DeviceBuffer(count * 2 * width * 4), DeviceBuffer(n * rb), DeviceBuffer((n + 1) * 4)]
     nodes, status, recs, offs = bufs
     try:
-        arr = (NsQuery * n)(*[NsQuery(*q) for q in queries])
+        arr = _records(NsQuery, queries)
         flat = b"".join(bytes(x) for x in nids)
         _check(L.rsm_proof_nodes_dev(ctx, buf.ptr, width, share_size, count, p, nodes.ptr, None, status.ptr, None))
         _check(L.rsm_ns_proofs_dev(ctx, nodes.ptr, status.ptr, buf.ptr, width, share_size, count, p, arr, flat, n,
@@ -1144,10 +1141,9 @@ def verify_namespaces_dev(records: "DeviceBuffer", offsets: "DeviceBuffer", shar
         return out
     st = DeviceBuffer(n * 4)
     try:
-        arr = (NsQuery * n)(*[NsQuery(*q) for q in queries])
         _check(L.rsm_ns_proofs_verify_dev(ctx, records.ptr, offsets.ptr, shares.ptr if shares is not None else None,
-                                          shares_total, roots.ptr, width, share_size, count, ctypes.byref(nmt), arr,
-                                          b"".join(bytes(x) for x in nids), n, st.ptr, None))
+                                          shares_total, roots.ptr, width, share_size, count, ctypes.byref(nmt),
+                                          _records(NsQuery, queries), b"".join(bytes(x) for x in nids), n, st.ptr, None))
         _check(L.rsm_sync(ctx))
         out[:] = st.download(n * 4).view(np.uint32)
     finally:
@@ -1353,8 +1349,8 @@ class ExtendedDataSquare:
         keep, fn, user = _tree_callback(tf)
         nmt = tf.params if isinstance(tf, ErasuredNamespacedMerkleTreeConstructor) else None
         L, w, S, n = library(), self.Width(), self.shareSize, len(samples)
-        arr = (Sample * max(n, 1))(*[Sample(0, a, i, p) for (a, i, p) in samples])
-        rb = int(L.rsm_proof_record_bytes(max(w, 1), ctypes.byref(nmt) if nmt is not None else None))
+        arr = _records(Sample, [(0, a, i, p) for (a, i, p) in samples])
+        rb = int(L.rsm_proof_record_bytes(max(w, 1), _nmt_ref(nmt)))
         rec = ctypes.create_string_buffer(max(n * rb, 1))
         sh = ctypes.create_string_buffer(max(n * S, 1))
         _check(L.rsm_eds_proofs(self._h, fn, user, arr, n, rec, sh))
@@ -1419,7 +1415,7 @@ class ExtendedDataSquare:
         keep, fn, user = _tree_callback(tf)
         if any(len(pr.share) != S for (_a, _i, _p, pr) in proofs):
             raise RSMError(RSM_EINVAL, "a sampled share is not of the square's share size")
-        arr = (Sample * max(n, 1))(*[Sample(0, a, i, p) for (a, i, p, _pr) in proofs])
+        arr = _records(Sample, [(0, a, i, p) for (a, i, p, _pr) in proofs])
         shares = b"".join(pr.share for (_a, _i, _p, pr) in proofs)
         records = b"".join(pr.record() for (_a, _i, _p, pr) in proofs)
         status = (ctypes.c_uint32 * max(n, 1))()

@@ -1,4 +1,5 @@
-// eds_internal.hpp -- the ExtendedDataSquare object, shared by eds.cpp and rsm_proof.cpp.
+// eds_internal.hpp -- the ExtendedDataSquare object, shared by eds.cpp and rsm_proof.cpp, and
+// the staging and range checks the device entry points share (rsm_proof.cpp, rsm_repair_dev.cpp).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,19 @@ namespace rsm {
 // (rsm_proof.cpp; ss.mu held): *dev is the device copy, valid for kernels enqueued on
 // `st` before the next call on it.
 int stage_bytes(hipStream_t st, StreamScratch& ss, const void* src, size_t bytes, const void** dev);
+// RSM_EINVAL, naming the first one, unless every sample addresses a cell of `count` squares
+// of `width` (rsm_proof.cpp).
+int check_samples(const char* fn, const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width);
+// The same for the (square, axis, index) that rsm_root_ref and rsm_ns_query begin with;
+// `noun`: "ref" or "query".
+template <class Ref>
+int check_refs(const char* fn, const char* noun, const Ref* r, uint32_t n, uint32_t count, uint32_t width) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (r[i].square >= count || r[i].axis > 1 || r[i].index >= width)
+            return fail(RSM_EINVAL, "%s: %s %u (square %u, axis %u, index %u) is out of range", fn, noun, i, r[i].square,
+                        r[i].axis, r[i].index);
+    return RSM_OK;
+}
 }  // namespace rsm
 
 // Host bytes of a square: pinned (hipHostMalloc) whenever a HIP runtime is

@@ -58,6 +58,14 @@ int stage_bytes(hipStream_t st, StreamScratch& ss, const void* src, size_t bytes
     return RSM_OK;
 }
 
+int check_samples(const char* fn, const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (s[i].square >= count || s[i].axis > 1 || s[i].index >= width || s[i].pos >= width)
+            return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", fn, i, s[i].square,
+                        s[i].axis, s[i].index, s[i].pos);
+    return RSM_OK;
+}
+
 }  // namespace rsm
 
 namespace {
@@ -72,16 +80,17 @@ uint64_t store_bytes(const DevTree& t, uint32_t W, uint32_t count) {
                       : proof_store_words(W, count, kProofShaWords, kProofShaWords));
 }
 
-// the first sample out of range, or n
-uint32_t first_bad_sample(const rsm_sample* s, uint32_t n, uint32_t count, uint32_t width) {
-    for (uint32_t i = 0; i < n; ++i)
-        if (s[i].square >= count || s[i].axis > 1 || s[i].index >= width || s[i].pos >= width) return i;
-    return n;
-}
-
-int bad_sample(const char* who, const rsm_sample* s, uint32_t i) {
-    return fail(RSM_EINVAL, "%s: sample %u (square %u, axis %u, index %u, pos %u) is out of range", who, i, s[i].square,
-                s[i].axis, s[i].index, s[i].pos);
+// The staged queries of the two namespace calls: the range check, then each namespace as
+// big-endian words, zero padded, as the leaf records hold them.
+int pack_ns_queries(const char* fn, const rsm_ns_query* queries, const uint8_t* nids, uint32_t n, uint32_t ns, uint32_t count,
+                    uint32_t width, std::vector<NsQuery>* out) {
+    if (int rc = check_refs(fn, "query", queries, n, count, width)) return rc;
+    out->assign(n, NsQuery{});
+    for (uint32_t i = 0; i < n; ++i) {
+        NsQuery& q = (*out)[i] = NsQuery{queries[i].square, queries[i].axis, queries[i].index, {}};
+        for (uint32_t b = 0; b < ns; ++b) q.nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
+    }
+    return RSM_OK;
 }
 
 int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
@@ -89,6 +98,33 @@ int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, 
     if (int rc = stage_bytes(st, ss, samples, (size_t)n * sizeof(rsm_sample), &d)) return rc;
     *ds = static_cast<const ProofSample*>(d);
     return RSM_OK;
+}
+
+// The two sample-verification calls: their checks before any device use, in their order
+// (`operands`: the call's pointers are all there), then the samples staged and
+// launch(staged samples, status words, stream); `what` names that launch in an error.
+template <class Launch>
+int verify_call(const char* fn, rsm_ctx* ctx, bool operands, const void* d_shares, void* d_status, uint32_t width,
+                uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n,
+                void* stream, const char* what, Launch launch) {
+    if (!ctx || width == 0 || width > 65536u || (n && count && !operands)) return fail(RSM_EINVAL, "%s: bad arguments", fn);
+    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
+        return fail(RSM_EINVAL, "%s: namespace size %u (1..32) or square size 0", fn, nmt->namespace_size);
+    if (reinterpret_cast<uintptr_t>(d_shares) & 15u) return fail(RSM_EINVAL, "%s: d_shares must be 16-byte aligned", fn);
+    if (reinterpret_cast<uintptr_t>(d_status) & 3u) return fail(RSM_EINVAL, "%s: d_status must be 4-byte aligned", fn);
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (n > (1u << 24)) return fail(RSM_EINVAL, "%s: at most %u samples per call", fn, 1u << 24);
+    if (n == 0 || count == 0) return RSM_OK;
+    if (int rc = check_samples(fn, samples, n, count, width)) return rc;
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const ProofSample* ds = nullptr;
+    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
+    const hipError_t e = launch(ds, static_cast<uint32_t*>(d_status), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, what);
 }
 
 uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -199,8 +235,7 @@ int rsm_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_
         return fail(RSM_EUNSUPPORTED, "rsm_proofs_dev: %u squares of width %u%s not supported", count, width,
                     nmt ? " (NMT)" : "");
     if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_dev: at most %u samples per call", 1u << 24);
-    const uint32_t bad = first_bad_sample(samples, n, count, width);
-    if (bad < n) return bad_sample("rsm_proofs_dev", samples, bad);
+    if (int rc = check_samples("rsm_proofs_dev", samples, n, count, width)) return rc;
     if (n == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
     hipStream_t st = pick(ctx, stream);
@@ -221,34 +256,16 @@ int rsm_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_
 int rsm_proofs_verify_dev(rsm_ctx* ctx, const void* d_shares, const void* d_records, const void* d_roots,
                           uint32_t width, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt,
                           const rsm_sample* samples, uint32_t n, void* d_status, void* stream) {
-    if (!ctx || width == 0 || width > 65536u || (n && count && (!samples || !d_shares || !d_records || !d_roots || !d_status)))
-        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: bad arguments");
-    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
-        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: namespace size %u (1..32) or square size 0", nmt->namespace_size);
-    if (reinterpret_cast<uintptr_t>(d_shares) & 15u)
-        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: d_shares must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_status) & 3u)
-        return fail(RSM_EINVAL, "rsm_proofs_verify_dev: d_status must be 4-byte aligned");
-    if (int rc = validate_chunk_size(share_size)) return rc;
-    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
-    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_verify_dev: at most %u samples per call", 1u << 24);
-    if (n == 0 || count == 0) return RSM_OK;
-    const uint32_t bad = first_bad_sample(samples, n, count, width);
-    if (bad < n) return bad_sample("rsm_proofs_verify_dev", samples, bad);
-    if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = pick(ctx, stream);
-    StreamScratch& ss = stream_scratch(ctx, st);
-    std::lock_guard<std::mutex> lk(ss.mu);
-    const ProofSample* ds = nullptr;
-    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
     const auto* sh = static_cast<const uint8_t*>(d_shares);
     const auto* rec = static_cast<const uint8_t*>(d_records);
     const auto* roots = static_cast<const uint8_t*>(d_roots);
-    const hipError_t e =
-        nmt ? launch_nmt_proof_verify(sh, rec, roots, width, share_size, nmt->namespace_size, nmt->square_size,
-                                      nmt->ignore_max_namespace, ds, n, static_cast<uint32_t*>(d_status), st)
-            : launch_proof_verify(sh, rec, roots, width, share_size, ds, n, static_cast<uint32_t*>(d_status), st);
-    return e == hipSuccess ? RSM_OK : hip_fail(e, "proof verify kernel launch");
+    return verify_call("rsm_proofs_verify_dev", ctx, samples && d_shares && d_records && d_roots && d_status, d_shares,
+                       d_status, width, share_size, count, nmt, samples, n, stream, "proof verify kernel launch",
+                       [&](const ProofSample* ds, uint32_t* status, hipStream_t st) {
+                           return nmt ? launch_nmt_proof_verify(sh, rec, roots, width, share_size, nmt->namespace_size,
+                                                                nmt->square_size, nmt->ignore_max_namespace, ds, n, status, st)
+                                      : launch_proof_verify(sh, rec, roots, width, share_size, ds, n, status, st);
+                       });
 }
 
 uint32_t rsm_data_root_record_bytes(uint32_t width) { return width == 0 ? 0 : 8 + proof_levels(2 * width) * 32; }
@@ -284,10 +301,7 @@ int rsm_root_proofs_dev(rsm_ctx* ctx, const void* d_nodes, uint32_t width, uint3
     if (!data_roots_dev_supported(width))
         return fail(RSM_EUNSUPPORTED, "rsm_root_proofs_dev: width %u not supported (at most %u)", width, kDataRootMaxWidth);
     if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_root_proofs_dev: at most %u refs per call", 1u << 24);
-    for (uint32_t i = 0; i < n; ++i)
-        if (refs[i].square >= count || refs[i].axis > 1 || refs[i].index >= width)
-            return fail(RSM_EINVAL, "rsm_root_proofs_dev: ref %u (square %u, axis %u, index %u) is out of range", i,
-                        refs[i].square, refs[i].axis, refs[i].index);
+    if (int rc = check_refs("rsm_root_proofs_dev", "ref", refs, n, count, width)) return rc;
     if (n == 0) return RSM_OK;
     if (int rc = use_device(ctx)) return rc;
     hipStream_t st = pick(ctx, stream);
@@ -304,37 +318,18 @@ int rsm_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_shares, const vo
                                     const void* d_data_roots, uint32_t width, uint32_t share_size, uint32_t count,
                                     const rsm_nmt_params* nmt, const rsm_sample* samples, uint32_t n, void* d_status,
                                     void* stream) {
-    if (!ctx || width == 0 || width > 65536u ||
-        (n && count && (!samples || !d_shares || !d_records || !d_root_records || !d_data_roots || !d_status)))
-        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: bad arguments");
-    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
-        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: namespace size %u (1..32) or square size 0",
-                    nmt->namespace_size);
-    if (reinterpret_cast<uintptr_t>(d_shares) & 15u)
-        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: d_shares must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_status) & 3u)
-        return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: d_status must be 4-byte aligned");
-    if (int rc = validate_chunk_size(share_size)) return rc;
-    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
-    if (n > (1u << 24)) return fail(RSM_EINVAL, "rsm_proofs_verify_data_root_dev: at most %u samples per call", 1u << 24);
-    if (n == 0 || count == 0) return RSM_OK;
-    const uint32_t bad = first_bad_sample(samples, n, count, width);
-    if (bad < n) return bad_sample("rsm_proofs_verify_data_root_dev", samples, bad);
-    if (int rc = use_device(ctx)) return rc;
-    hipStream_t st = pick(ctx, stream);
-    StreamScratch& ss = stream_scratch(ctx, st);
-    std::lock_guard<std::mutex> lk(ss.mu);
-    const ProofSample* ds = nullptr;
-    if (int rc = stage_samples(st, ss, samples, n, &ds)) return rc;
     const auto* sh = static_cast<const uint8_t*>(d_shares);
     const auto* rec = static_cast<const uint8_t*>(d_records);
     const auto* rrec = static_cast<const uint8_t*>(d_root_records);
     const auto* dr = static_cast<const uint8_t*>(d_data_roots);
-    const hipError_t e =
-        nmt ? launch_nmt_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, nmt->namespace_size, nmt->square_size,
-                                                nmt->ignore_max_namespace, ds, n, static_cast<uint32_t*>(d_status), st)
-            : launch_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, ds, n, static_cast<uint32_t*>(d_status), st);
-    return e == hipSuccess ? RSM_OK : hip_fail(e, "chained proof verify kernel launch");
+    return verify_call(
+        "rsm_proofs_verify_data_root_dev", ctx, samples && d_shares && d_records && d_root_records && d_data_roots && d_status,
+        d_shares, d_status, width, share_size, count, nmt, samples, n, stream, "chained proof verify kernel launch",
+        [&](const ProofSample* ds, uint32_t* status, hipStream_t st) {
+            return nmt ? launch_nmt_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, nmt->namespace_size,
+                                                           nmt->square_size, nmt->ignore_max_namespace, ds, n, status, st)
+                       : launch_proof_verify_data_root(sh, rec, rrec, dr, width, share_size, ds, n, status, st);
+        });
 }
 
 int rsm_eds_data_root(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, uint8_t* out) {
@@ -404,8 +399,7 @@ int rsm_eds_import_samples(rsm_eds* e, const uint8_t* row_roots, const uint8_t* 
     const uint32_t NL = nmt ? 2 * nmt->namespace_size + 32 : 32, RB = 8 + proof_levels(W) * NL;
     if (root_len != NL) return fail(RSM_EINVAL, "rsm_eds_import_samples: roots of %u bytes, the tree's have %u", root_len, NL);
     if (nmt && S < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
-    const uint32_t bad = first_bad_sample(samples, n, 1, W);
-    if (bad < n) return bad_sample("rsm_eds_import_samples", samples, bad);
+    if (int rc = check_samples("rsm_eds_import_samples", samples, n, 1, W)) return rc;
     if (accepted) *accepted = 0;
     if (n == 0) return RSM_OK;
     std::vector<uint32_t> status(n);
@@ -471,8 +465,7 @@ int rsm_eds_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_s
     if (!nmt && tree_fn != nullptr && tree_fn != rsm_default_tree_root)
         return fail(RSM_EUNSUPPORTED, "rsm_eds_proofs: proofs are built for the DefaultTree and the NMT only");
     const uint32_t W = e->width, S = e->S;
-    const uint32_t bad = first_bad_sample(samples, n, 1, W);
-    if (bad < n) return bad_sample("rsm_eds_proofs", samples, bad);
+    if (int rc = check_samples("rsm_eds_proofs", samples, n, 1, W)) return rc;
     const uint32_t RB = rsm_proof_record_bytes(W, nmt);
     if (n && RB == 0) return fail(RSM_EINVAL, "rsm_eds_proofs: namespace size 0");
     auto cell_of = [&](const rsm_sample& s) { return e->cell(e->rr((int)s.axis, s.index, s.pos), e->cc((int)s.axis, s.index, s.pos)); };
@@ -539,15 +532,8 @@ int rsm_ns_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status, c
     if (n > (1u << 20)) return fail(RSM_EINVAL, "rsm_ns_proofs_dev: at most %u queries per call", 1u << 20);
     if (n == 0 || count == 0) return RSM_OK;
     const uint32_t ns = t.p.namespace_size;
-    std::vector<NsQuery> q(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (queries[i].square >= count || queries[i].axis > 1 || queries[i].index >= width)
-            return fail(RSM_EINVAL, "rsm_ns_proofs_dev: query %u (square %u, axis %u, index %u) is out of range", i,
-                        queries[i].square, queries[i].axis, queries[i].index);
-        q[i] = NsQuery{queries[i].square, queries[i].axis, queries[i].index, {}};
-        for (uint32_t b = 0; b < ns; ++b)  // big-endian words, zero padded, as the leaf records
-            q[i].nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
-    }
+    std::vector<NsQuery> q;
+    if (int rc = pack_ns_queries("rsm_ns_proofs_dev", queries, nids, n, ns, count, width, &q)) return rc;
     if (int rc = use_device(ctx)) return rc;
     hipStream_t st = pick(ctx, stream);
     StreamScratch& ss = stream_scratch(ctx, st);
@@ -583,15 +569,8 @@ int rsm_ns_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_
     if (n > (1u << 20)) return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: at most %u queries per call", 1u << 20);
     if (n == 0 || count == 0) return RSM_OK;
     const uint32_t ns = nmt->namespace_size;
-    std::vector<NsQuery> q(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (queries[i].square >= count || queries[i].axis > 1 || queries[i].index >= width)
-            return fail(RSM_EINVAL, "rsm_ns_proofs_verify_dev: query %u (square %u, axis %u, index %u) is out of range", i,
-                        queries[i].square, queries[i].axis, queries[i].index);
-        q[i] = NsQuery{queries[i].square, queries[i].axis, queries[i].index, {}};
-        for (uint32_t b = 0; b < ns; ++b)  // big-endian words, zero padded, as rsm_ns_proofs_dev stages them
-            q[i].nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
-    }
+    std::vector<NsQuery> q;
+    if (int rc = pack_ns_queries("rsm_ns_proofs_verify_dev", queries, nids, n, ns, count, width, &q)) return rc;
     if (int rc = use_device(ctx)) return rc;
     hipStream_t st = pick(ctx, stream);
     StreamScratch& ss = stream_scratch(ctx, st);
