@@ -869,6 +869,59 @@ int rsm_samples_scatter_dev(rsm_ctx* ctx, void* d_eds, void* d_presence, uint32_
                             uint32_t count, const rsm_sample* samples, uint32_t n, const void* d_shares,
                             void* d_status, void* stream);
 
+/* ---- bad-encoding fraud proofs --------------------------------------------------------
+ * The last step of the sampling flow: a node that receives the shares of a vector named by
+ * rsm_repair_squares_checked_dev (ErrByzantineData.Shares, as rsm_vectors_gather_dev packs
+ * them), each with its Merkle proof in the ORTHOGONAL tree, decides whether the vector is
+ * badly encoded -- the reference's PseudoFraudProof (extendeddatacrossword_test.go:19-21,
+ * 143-162) with the per-share proofs its TODO asks for.  n proofs are validated per call.
+ *
+ * Proof i claims that vector refs[i] = (square, axis, index) of a batch of `count` squares
+ * of width 2k is badly encoded.  d_shares [n][2k][share_size] (16-byte aligned) and
+ * d_present [n][2k] bytes are what rsm_vectors_gather_dev writes.  d_records
+ * [n][2k][rsm_proof_record_bytes(2k, nmt)] (any alignment): record (i, j) proves leaf
+ * pos = index of tree (axis ^ 1, j) -- what rsm_proofs_dev writes for the samples
+ * rsm_fraud_proof_samples lists, so prove -> gather -> validate needs no repacking.
+ * d_roots: the committed table [count][2][2k][root_len] of the repair calls.  refs and
+ * verdicts are HOST memory (n each).  The first rule that applies gives the verdict:
+ *   1. fewer than k presence bytes are non-zero: RSM_FRAUD_TOOFEW;
+ *   2. a present slot j whose share does not verify against root (square, axis ^ 1, j) at
+ *      position index, by rsm_proofs_verify_dev's contract: RSM_FRAUD_SHARE, pos = the lowest
+ *      such j, reason = its RSM_PROOF_* word (a minimum over keys: no lane order shows);
+ *   3. the missing slots are decoded from the present ones (a vector with all 2k present is
+ *      taken as it is) and the rebuilt vector gets rsm_repair_squares_checked_dev's check in
+ *      its order -- the NMT tree's status (quadrant rule index < square_size && pos <
+ *      square_size), the root against committed root (square, axis, index), the parity
+ *      against a re-encode of the first half: RSM_FRAUD_VALID with that RSM_BYZ_* reason;
+ *   4. otherwise RSM_FRAUD_CONSISTENT.
+ * A slot whose presence byte is non-zero is never written; d_present, d_records and d_roots
+ * are never written; nothing is stored outside the missing slots of d_shares and d_work
+ * (rsm_fraud_work_bytes bytes, 16-byte aligned).  For VALID and CONSISTENT the missing slots
+ * hold the decoded shares on return, for TOOFEW and SHARE unspecified bytes.  No output
+ * depends on the share or record bytes of an absent slot.  The call returns after everything
+ * it enqueued on `stream` has completed.
+ * Limits: those of the device trees (2k <= 2048; NMT: 2k <= 1024, namespace size 1..32,
+ * 2k <= 2 * square_size), n <= 65535 and n * 2k <= 2^24: RSM_EUNSUPPORTED beyond them, and
+ * rsm_fraud_work_bytes is 0 exactly there.  Argument errors as rsm_repair_squares_dev and
+ * rsm_vectors_gather_dev; n == 0 or count == 0 launches nothing. */
+#define RSM_FRAUD_VALID 0       /* the proof holds: the vector is bad; reason = RSM_BYZ_TREE / _ROOT / _ENCODING */
+#define RSM_FRAUD_TOOFEW 1      /* fewer than k slots present; nothing else was evaluated */
+#define RSM_FRAUD_SHARE 2       /* a present share does not verify under its orthogonal committed root:
+                                   pos = the lowest such slot, reason = its RSM_PROOF_* status word */
+#define RSM_FRAUD_CONSISTENT 3  /* every share verifies and the rebuilt vector passes all three checks: no fraud */
+typedef struct {
+    uint32_t verdict, reason, pos, present; /* present: non-zero presence bytes */
+} rsm_fraud_verdict;
+uint64_t rsm_fraud_work_bytes(uint32_t k, uint32_t share_size, uint32_t n, const rsm_nmt_params* nmt);
+/* Host only: samples_out[j] = {ref->square, ref->axis ^ 1, j, ref->index} for j < 2k, the
+ * samples whose rsm_proofs_dev records are proof `ref`'s row of d_records.  RSM_EINVAL for a
+ * null operand, k == 0 or k > 32768, an axis above 1 or index >= 2k. */
+int rsm_fraud_proof_samples(const rsm_root_ref* ref, uint32_t k, rsm_sample* samples_out /* [2k] */);
+int rsm_fraud_proofs_verify_dev(rsm_ctx* ctx, void* d_shares, const void* d_present, const void* d_records,
+                                const void* d_roots, uint32_t k, uint32_t share_size, uint32_t count,
+                                const rsm_nmt_params* nmt, const rsm_root_ref* refs, uint32_t n, void* d_work,
+                                rsm_fraud_verdict* verdicts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

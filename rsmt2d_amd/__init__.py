@@ -41,6 +41,8 @@ __all__ = [
     "REPAIR_OK", "REPAIR_STUCK", "REPAIR_ENCODING", "REPAIR_ROOTS",
     "REPAIR_BYZANTINE", "BYZ_ROOT", "BYZ_ENCODING", "BYZ_TREE", "RepairCheck", "repair_squares_checked_dev",
     "gather_vectors_dev", "byzantine_data_dev",
+    "FRAUD_VALID", "FRAUD_TOOFEW", "FRAUD_SHARE", "FRAUD_CONSISTENT", "FraudVerdict", "fraud_proof_samples",
+    "verify_fraud_proofs_dev", "BadEncodingProof",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -145,6 +147,18 @@ class RepairCheck(ctypes.Structure):
     """rsm_repair_check (include/rsmt2d_hip.h): one square of rsm_repair_squares_checked_dev."""
     _fields_ = [("axis", ctypes.c_uint32), ("index", ctypes.c_uint32), ("round", ctypes.c_uint32),
                 ("reason", ctypes.c_uint32), ("checked_vectors", ctypes.c_uint32), ("hashed_cells", ctypes.c_uint32)]
+
+
+#: rsm_fraud_verdict.verdict of rsm_fraud_proofs_verify_dev (include/rsmt2d_hip.h)
+FRAUD_VALID, FRAUD_TOOFEW, FRAUD_SHARE, FRAUD_CONSISTENT = 0, 1, 2, 3
+
+
+class FraudVerdict(ctypes.Structure):
+    """rsm_fraud_verdict (include/rsmt2d_hip.h): one proof of rsm_fraud_proofs_verify_dev.
+    ``reason``: BYZ_* of a FRAUD_VALID proof, the RSM_PROOF_* word of slot ``pos`` of a
+    FRAUD_SHARE one; ``present``: the non-zero presence bytes."""
+    _fields_ = [("verdict", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("pos", ctypes.c_uint32),
+                ("present", ctypes.c_uint32)]
 
 
 # (name, restype, argtypes) of every symbol declared in include/rsmt2d_hip.h
@@ -268,6 +282,10 @@ SIGNATURES = {
                                               ctypes.POINTER(RepairResult), ctypes.POINTER(RepairCheck), _VP]),
     "rsm_vectors_gather_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _VP]),
     "rsm_samples_scatter_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _VP]),
+    "rsm_fraud_work_bytes": (_U64, [_U32, _U32, _U32, ctypes.POINTER(NmtParams)]),
+    "rsm_fraud_proof_samples": (_I32, [_VP, _U32, _VP]),
+    "rsm_fraud_proofs_verify_dev": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _U32,
+                                           _VP, ctypes.POINTER(FraudVerdict), _VP]),
 }
 
 
@@ -890,6 +908,80 @@ def byzantine_data_dev(eds_buf: "DeviceBuffer", presence_buf: "DeviceBuffer", k:
 
 
 # ---------------------------------------------------------------------------
+# Bad-encoding fraud proofs (include/rsmt2d_hip.h "bad-encoding fraud proofs")
+# ---------------------------------------------------------------------------
+def fraud_proof_samples(axis: int, index: int, k: int, square: int = 0) -> List[tuple]:
+    """The ``(square, axis ^ 1, j, index)`` samples, j < 2k, whose proofs a fraud proof of
+    vector (square, axis, index) carries (rsm_fraud_proof_samples)."""
+    out = (Sample * max(2 * k, 1))()
+    _check(library().rsm_fraud_proof_samples(ctypes.byref(RootRef(square, axis, index)), k, out))
+    return [(s.square, s.axis, s.index, s.pos) for s in out[:2 * k]]
+
+
+def verify_fraud_proofs_dev(shares: "DeviceBuffer", present: "DeviceBuffer", records: "DeviceBuffer",
+                            roots: "DeviceBuffer", k: int, share_size: int, refs: Sequence[tuple], count: int = 1,
+                            nmt: Optional[NmtParams] = None) -> List[FraudVerdict]:
+    """Validates ``len(refs)`` bad-encoding fraud proofs (rsm_fraud_proofs_verify_dev): proof
+    i accuses vector ``refs[i] = (square, axis, index)``; ``shares`` [n][2k][share_size] and
+    ``present`` [n][2k] as ``rsm_vectors_gather_dev`` writes them, ``records`` [n][2k] proof
+    records of the shares in their orthogonal trees (the samples of ``fraud_proof_samples``),
+    ``roots`` the committed table.  One FraudVerdict per proof; the missing slots of
+    ``shares`` hold the decoded shares of a FRAUD_VALID or FRAUD_CONSISTENT proof."""
+    L, ctx, n, p = library(), shares.ctx, len(refs), _nmt_ref(nmt)
+    nbytes = int(L.rsm_fraud_work_bytes(k, share_size, n, p))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"fraud proofs: {n} proofs of width {2 * k} not supported")
+    out = (FraudVerdict * max(n, 1))()
+    work = DeviceBuffer(nbytes)
+    try:
+        _check(L.rsm_fraud_proofs_verify_dev(ctx, shares.ptr, present.ptr, records.ptr, roots.ptr, k, share_size, count, p,
+                                             _records(RootRef, refs), n, work.ptr, out, None))
+    finally:
+        work.free()
+    return list(out[:n])
+
+
+class BadEncodingProof:
+    """The claim that row / column ``index`` (``axis``) of a square is badly encoded: the
+    vector's ``shares`` (None where the prover has none) and for each a ``Proof`` in its
+    ORTHOGONAL tree -- the reference's PseudoFraudProof (extendeddatacrossword_test.go:19-21)
+    with the Merkle proof per share its TODO asks for."""
+
+    def __init__(self, axis: int, index: int, shares: Sequence[Optional[bytes]], proofs: Sequence[Optional["Proof"]]):
+        self.axis, self.index, self.shares, self.proofs = axis, index, list(shares), list(proofs)
+
+    def Validate(self, rowRoots: Sequence[bytes], colRoots: Sequence[bytes], codec: Codec,
+                 treeCreatorFn=NewDefaultTree) -> FraudVerdict:
+        """The verdict of this proof against the committed roots, decided on the device of
+        ``codec``: FRAUD_VALID (with ``reason``) when the proof holds."""
+        import numpy as np
+        nmt = treeCreatorFn.params if isinstance(treeCreatorFn, ErasuredNamespacedMerkleTreeConstructor) else None
+        W = len(self.shares)
+        have = [s for s in self.shares if s is not None]
+        if W == 0 or W % 2 or len(self.proofs) != W or not have or len(rowRoots) != W or len(colRoots) != W:
+            raise RSMError(RSM_EINVAL, "a fraud proof carries 2k slots, a share in one at least, and 2k roots per axis")
+        S = len(have[0])
+        rb = int(library().rsm_proof_record_bytes(W, _nmt_ref(nmt)))
+        sh, pr, rec = np.zeros((W, S), np.uint8), np.zeros(W, np.uint8), np.zeros((W, rb), np.uint8)
+        for j, (s, p) in enumerate(zip(self.shares, self.proofs)):
+            if s is None:
+                continue
+            if len(s) != S or p is None:
+                raise RSMError(RSM_EINVAL, "every share of a fraud proof has the same size and a proof")
+            sh[j], pr[j], rec[j] = np.frombuffer(s, np.uint8), 1, np.frombuffer(p.record(), np.uint8)
+        table = np.frombuffer(b"".join(bytes(r) for r in list(rowRoots) + list(colRoots)), np.uint8)
+        dev = _device_of(codec)
+        bufs = [DeviceBuffer(max(a.nbytes, 16), dev) for a in (sh, pr, rec, table)]
+        try:
+            for b, a in zip(bufs, (sh, pr, rec, table)):
+                b.upload(a.reshape(-1))
+            return verify_fraud_proofs_dev(*bufs, W // 2, S, [(0, self.axis, self.index)], 1, nmt)[0]
+        finally:
+            for b in bufs:
+                b.free()
+
+
+# ---------------------------------------------------------------------------
 # Data root (include/rsmt2d_hip.h "data root")
 # ---------------------------------------------------------------------------
 class RootRef(ctypes.Structure):
@@ -1364,6 +1456,16 @@ class ExtendedDataSquare:
     def ColProof(self, rowIdx: int, colIdx: int) -> "Proof":
         """Share (rowIdx, colIdx) with its proof against ColRoots()[colIdx]."""
         return self.Proofs([(Col, colIdx, rowIdx)])[0]
+
+    def BadEncodingProof(self, axis: int, index: int) -> "BadEncodingProof":
+        """The fraud proof a node holding this complete, committed square gives for its row
+        (``axis`` = Row) or column ``index``: every share of the vector, each with its proof in
+        the orthogonal tree (``Proofs``).  ``.Validate`` decides it against the committed roots."""
+        w = self.Width()
+        shares = self.Row(index) if axis == Row else self.Col(index)
+        if any(s is None for s in shares):
+            raise RSMError(RSM_EINVAL, "a fraud proof is built from a complete square")
+        return BadEncodingProof(axis, index, shares, self.Proofs([(axis ^ 1, j, index) for j in range(w)]))
 
     # --- namespace proofs (rsm_eds_namespace_proofs) ---
     def NamespaceProofs(self, nid: bytes, axis: int = 0, indices: Optional[Sequence[int]] = None) -> List["NamespaceProof"]:

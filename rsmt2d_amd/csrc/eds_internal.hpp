@@ -1,5 +1,6 @@
 // eds_internal.hpp -- the ExtendedDataSquare object, shared by eds.cpp and rsm_proof.cpp, and
-// the staging and range checks the device entry points share (rsm_proof.cpp, rsm_repair_dev.cpp).
+// the staging, range checks and scratch carving the device entry points share (rsm_proof.cpp,
+// rsm_repair_dev.cpp, rsm_fraud.cpp).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +27,26 @@ int check_refs(const char* fn, const char* noun, const Ref* r, uint32_t n, uint3
                         r[i].axis, r[i].index);
     return RSM_OK;
 }
+
+// Hands out the sections of a d_work: each a multiple of 256 bytes from its start.
+struct Carver {
+    uint64_t at = 0;
+    uint64_t take(uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) / 256 * 256;
+        return o;
+    }
+};
+
+// An early return must not hand the lane's pinned staging back while the stream still
+// reads or writes it.
+struct Drain {
+    hipStream_t st;
+    bool armed;
+    ~Drain() {
+        if (armed) (void)hipStreamSynchronize(st);
+    }
+};
 }  // namespace rsm
 
 // Host bytes of a square: pinned (hipHostMalloc) whenever a HIP runtime is

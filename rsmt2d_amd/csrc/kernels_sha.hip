@@ -29,8 +29,6 @@ namespace rsm {
 
 namespace {
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
 // leaf[cell][8] = SHA256(0x00 || share(cell)), cell = row * W + col.
 __global__ __launch_bounds__(256) void leaf_hash_kernel(const uint8_t* __restrict__ eds, uint32_t cells,
                                                         uint32_t S, uint32_t* __restrict__ leaf) {
@@ -347,36 +345,8 @@ __global__ __launch_bounds__(256) void tree_nodes_kernel(uint32_t* __restrict__ 
 // (two compressions each) and compares with its root: no intermediate buffer.  Records
 // sit at any alignment (memcpy loads: gfx950 global loads need none); nothing past the
 // derived nodes is read, and no address depends on what a record or a share holds.
-// (proof_shape, fold_digests: dataroot_dev.hpp, shared with the chained kernels.)
-
-// the leaf digest of a share (S a multiple of 64, 16-byte aligned), as leaf_hash_kernel
-__device__ __forceinline__ void share_leaf_hash(const uint8_t* share, uint32_t S, uint32_t (&h)[8]) {
-    const v4u* p = reinterpret_cast<const v4u*>(share);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = kH0[i];
-    uint32_t prev = 0;  // the 0x00 leaf prefix
-    for (uint32_t blk = 0; blk < S / 64u; ++blk) {
-        uint32_t w[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const v4u v = p[blk * 4u + q];
-            const uint32_t b0 = __builtin_bswap32(v.x), b1 = __builtin_bswap32(v.y);
-            const uint32_t b2 = __builtin_bswap32(v.z), b3 = __builtin_bswap32(v.w);
-            w[4 * q + 0] = shift8(prev, b0);
-            w[4 * q + 1] = shift8(b0, b1);
-            w[4 * q + 2] = shift8(b1, b2);
-            w[4 * q + 3] = shift8(b2, b3);
-            prev = b3;
-        }
-        sha_block(h, w);
-    }
-    uint32_t w[16];
-    w[0] = (prev << 24) | 0x00800000u;
-#pragma unroll
-    for (int i = 1; i < 15; ++i) w[i] = 0;
-    w[15] = (S + 1u) * 8u;
-    sha_block(h, w);
-}
+// (proof_shape, fold_digests: dataroot_dev.hpp, shared with the chained kernels;
+// share_leaf_hash, the leaf digest of a share: sha256_dev.hpp, shared with kernels_fraud.hip.)
 
 __global__ __launch_bounds__(256) void proof_verify_kernel(const uint8_t* __restrict__ shares,
                                                            const uint8_t* __restrict__ records,
@@ -532,13 +502,9 @@ __global__ __launch_bounds__(256) void list_leaf_hash_kernel(const uint8_t* __re
     if (b && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(b)) atomicAdd(&hashed[s], (uint32_t)__popcll(b));
 }
 
-// One tree per wave (entry blockIdx.x * 4 + wave of square blockIdx.y), by levels in the
-// wave's own LDS (ceil(W / 2) digests): node (l, j) over leaves [j 2^l, min((j + 1) 2^l,
-// W)), an unpaired last node carried up unchanged -- tree_nodes_kernel's picture, the same
-// tree as tree_root_kernel's stack of subtrees.  A level is built in place (node j reads
-// 2j and 2j + 1 >= j; a 64-node pass reads before it writes, later passes read beyond
-// what it wrote), level 1 from the records.  Lane 0 compares the root with the committed
-// one.
+// One tree per wave (entry blockIdx.x * 4 + wave of square blockIdx.y) in the wave's own
+// LDS (wave_tree_levels, sha256_dev.hpp), the leaves along the row or strided down the
+// column.  Lane 0 compares the root with the committed one.
 __global__ __launch_bounds__(256) void list_tree_check_kernel(const uint32_t* __restrict__ leaf, uint32_t W,
                                                               const uint32_t* __restrict__ list,
                                                               const uint32_t* __restrict__ cnt,
@@ -551,57 +517,14 @@ __global__ __launch_bounds__(256) void list_tree_check_kernel(const uint32_t* __
     if (!list_entry(list, cnt, W, s, blockIdx.x * 4u + wv, &axis, &index, &slot)) return;  // the whole wave
     uint32_t* const lv = lds_raw + (size_t)wv * ((W + 1) / 2) * 8u;
     leaf += (uint64_t)s * W * W * 8u;
-    auto leaf_at = [&](uint32_t pos, uint32_t (&d)[8]) {
-        const uint64_t cell = axis == 0 ? (uint64_t)index * W + pos : (uint64_t)pos * W + index;
-        const v4u* p = reinterpret_cast<const v4u*>(leaf + cell * 8u);
-        const v4u a = p[0], b = p[1];
-        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
-    };
-    uint32_t prev = W;
-    for (uint32_t l = 1; prev > 1; ++l) {
-        const uint32_t n = (prev + 1) / 2;
-        for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
-            const uint32_t j = j0 + lane;
-            uint32_t a[8], b[8], o[8];
-            const bool act = j < n, pair = 2 * j + 1 < prev;
-            if (act) {
-                if (l == 1) {
-                    leaf_at(2 * j, a);
-                    if (pair) leaf_at(2 * j + 1, b);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        a[q] = lv[(2 * j) * 8u + q];
-                        b[q] = pair ? lv[(2 * j + 1) * 8u + q] : 0u;
-                    }
-                }
-                if (pair) {
-                    node_hash(a, b, o);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) o[q] = a[q];
-                }
-            }
-            // every read of this pass precedes its in-place writes
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (act) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) lv[j * 8u + q] = o[q];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        prev = n;
-    }
-    if (lane == 0) {
-        const uint8_t* rt = committed + (((uint64_t)s * 2u + axis) * W + index) * 32u;
-        uint32_t diff = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) diff |= lv[q] ^ __builtin_bswap32(ld_u32(rt + 4 * q));
-        verdict[slot] = diff ? kByzRoot : 0u;
-    }
+    wave_tree_levels(
+        [&](uint32_t pos) {
+            const uint64_t cell = axis == 0 ? (uint64_t)index * W + pos : (uint64_t)pos * W + index;
+            return leaf + cell * 8u;
+        },
+        W, lv, lane);
+    if (lane == 0)
+        verdict[slot] = digest_differs(lv, committed + (((uint64_t)s * 2u + axis) * W + index) * 32u) ? kByzRoot : 0u;
 }
 
 }  // namespace

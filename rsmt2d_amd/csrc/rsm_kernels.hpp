@@ -420,6 +420,37 @@ hipError_t launch_vectors_gather(const uint8_t* d_eds, const uint8_t* d_presence
 hipError_t launch_samples_scatter(const ProofSample* d_samples, const uint32_t* d_prev, uint32_t* d_verdict,
                                   const uint8_t* d_shares, uint8_t* d_eds, uint8_t* d_presence, uint32_t* d_status,
                                   uint32_t W, uint32_t S, uint32_t n, hipStream_t st);
+// ---- fraud proofs (rsm_fraud_proofs_verify_dev; DESIGN.md §5 "Fraud proofs"; kernels_fraud.hip) ----
+// n proofs as packed vectors: d_shares [n][W][S] (16-byte aligned), d_present [n][W], as
+// launch_vectors_gather writes them; d_refs[i]: the vector proof i accuses (validated on the
+// host).  The proofs are taken in chunks of W: chunk c is rows [c W, min((c + 1) W, n)) of
+// d_shares, which the decoders and encoders address as rows of one square.
+constexpr uint32_t kFraudValid = 0, kFraudTooFew = 1, kFraudShare = 2, kFraudConsistent = 3;
+bool fraud_supported(uint32_t W, uint32_t ns);  // ns = 0: DefaultTree
+// Two launches.  d_have [n]: non-zero presence bytes of each proof; d_samples [n][W]: slot j
+// of proof i as {square, axis ^ 1, j, index}, the sample its record proves; d_dec_list,
+// d_chk_list [chunks][W]: per chunk the chunk-local rows with k <= have < W and with
+// have >= k, ascending; d_slot [n]: a checked proof's word of d_chk_list (and of the parity
+// flags), ~0 otherwise; report (pinned, mapped): two words per chunk, the lists' lengths.
+hipError_t launch_fraud_plan(const uint8_t* d_present, const RootRef* d_refs, uint32_t W, uint32_t n, uint32_t* d_have,
+                             ProofSample* d_samples, uint32_t* d_dec_list, uint32_t* d_chk_list, uint32_t* d_slot,
+                             uint32_t* report, hipStream_t st);
+// Leaf records of every proof with have >= k (d_leaf: [n][W] records of 8 words, NMT 16; the
+// NMT namespace of (i, pos) is the share's own when d_refs[i].index < sq and pos < sq),
+// then one tree per such proof, compared with committed root (square, axis, index) of
+// d_committed ([squares][2][W][root_len], any alignment): d_tree[i] receives 0, kByzRoot or
+// (NMT, consulted first) kByzTree.
+hipError_t launch_fraud_trees(const uint8_t* d_shares, const uint32_t* d_have, const RootRef* d_refs, uint32_t W, uint32_t S,
+                              uint32_t n, uint32_t ns, uint32_t sq, uint32_t ignore_max, const uint8_t* d_committed,
+                              uint32_t* d_leaf, uint32_t* d_tree, hipStream_t st);
+// The verdict records, four words per proof (rsm_fraud_verdict) into `out` (16-byte aligned;
+// pinned and mapped, or device memory): kFraudTooFew below k; else kFraudShare with the
+// lowest present slot whose word of d_status ([n][W], the verify kernels') is non-zero; else
+// kFraudValid with d_tree's word or kByzEncoding where the proof's parity flag
+// (d_parity[d_slot[i]], launch_compare_parity's) is set; else kFraudConsistent.
+hipError_t launch_fraud_verdicts(const uint8_t* d_present, const uint32_t* d_have, const uint32_t* d_status,
+                                 const uint32_t* d_tree, const uint32_t* d_slot, const uint32_t* d_parity, uint32_t W,
+                                 uint32_t n, uint32_t* out, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

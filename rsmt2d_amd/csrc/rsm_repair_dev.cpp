@@ -23,16 +23,6 @@ static_assert(RSM_PROOF_OCCUPIED == 4, "the scatter kernel's OCCUPIED word is th
 
 namespace {
 
-// Hands out the sections of a d_work: each a multiple of 256 bytes from its start.
-struct Carver {
-    uint64_t at = 0;
-    uint64_t take(uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 255) / 256 * 256;
-        return o;
-    }
-};
-
 // Sections of d_work.
 struct WorkLayout {
     uint64_t todo[2];  // [count][W] words each: the lists of this pass and the one before
@@ -130,16 +120,6 @@ int repair_args(const char* fn, rsm_ctx* ctx, const void* d_eds, const void* d_p
     if (t.nmt && share_size < t.p.namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
     return RSM_OK;
 }
-
-// An early return must not hand the lane's pinned staging back while the stream still
-// reads or writes it.
-struct Drain {
-    hipStream_t st;
-    bool armed;
-    ~Drain() {
-        if (armed) (void)hipStreamSynchronize(st);
-    }
-};
 
 // What a Repair call holds from its argument checks to its return (the device selected).
 struct Session {

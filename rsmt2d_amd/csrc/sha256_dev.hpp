@@ -80,5 +80,98 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
     return v;
 }
 
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// the leaf digest of a share (S a multiple of 64, 16-byte aligned), as leaf_hash_kernel
+__device__ __forceinline__ void share_leaf_hash(const uint8_t* share, uint32_t S, uint32_t (&h)[8]) {
+    const v4u* p = reinterpret_cast<const v4u*>(share);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = kH0[i];
+    uint32_t prev = 0;  // the 0x00 leaf prefix
+    for (uint32_t blk = 0; blk < S / 64u; ++blk) {
+        uint32_t w[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4u v = p[blk * 4u + q];
+            const uint32_t b0 = __builtin_bswap32(v.x), b1 = __builtin_bswap32(v.y);
+            const uint32_t b2 = __builtin_bswap32(v.z), b3 = __builtin_bswap32(v.w);
+            w[4 * q + 0] = shift8(prev, b0);
+            w[4 * q + 1] = shift8(b0, b1);
+            w[4 * q + 2] = shift8(b1, b2);
+            w[4 * q + 3] = shift8(b2, b3);
+            prev = b3;
+        }
+        sha_block(h, w);
+    }
+    uint32_t w[16];
+    w[0] = (prev << 24) | 0x00800000u;
+#pragma unroll
+    for (int i = 1; i < 15; ++i) w[i] = 0;
+    w[15] = (S + 1u) * 8u;
+    sha_block(h, w);
+}
+
+// One DefaultTree per wave, by levels in the wave's own LDS `lv` (ceil(W / 2) digests of 8
+// words; W >= 2): node (l, j) over leaves [j 2^l, min((j + 1) 2^l, W)), an unpaired last
+// node carried up unchanged -- tree_nodes_kernel's picture, the same tree as
+// tree_root_kernel's stack of subtrees.  A level is built in place (node j reads 2j and
+// 2j + 1 >= j; a 64-node pass reads before it writes, later passes read beyond what it
+// wrote), level 1 from the leaf records: record_at(pos) is leaf pos' 8 words, 16-byte
+// aligned.  The root is lv[0 .. 7] when it returns.
+template <class RecordAt>
+__device__ __forceinline__ void wave_tree_levels(RecordAt&& record_at, uint32_t W, uint32_t* lv, uint32_t lane) {
+    auto leaf_at = [&](uint32_t pos, uint32_t (&d)[8]) {
+        const v4u* p = reinterpret_cast<const v4u*>(record_at(pos));
+        const v4u a = p[0], b = p[1];
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+    };
+    uint32_t prev = W;
+    for (uint32_t l = 1; prev > 1; ++l) {
+        const uint32_t n = (prev + 1) / 2;
+        for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
+            const uint32_t j = j0 + lane;
+            uint32_t a[8], b[8], o[8];
+            const bool act = j < n, pair = 2 * j + 1 < prev;
+            if (act) {
+                if (l == 1) {
+                    leaf_at(2 * j, a);
+                    if (pair) leaf_at(2 * j + 1, b);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        a[q] = lv[(2 * j) * 8u + q];
+                        b[q] = pair ? lv[(2 * j + 1) * 8u + q] : 0u;
+                    }
+                }
+                if (pair) {
+                    node_hash(a, b, o);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) o[q] = a[q];
+                }
+            }
+            // every read of this pass precedes its in-place writes
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (act) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) lv[j * 8u + q] = o[q];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        prev = n;
+    }
+}
+
+// whether the digest d (8 big-endian words) differs from the 32 bytes at rt (any alignment)
+__device__ __forceinline__ bool digest_differs(const uint32_t* d, const uint8_t* rt) {
+    uint32_t diff = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) diff |= d[q] ^ __builtin_bswap32(ld_u32(rt + 4 * q));
+    return diff != 0;
+}
+
 }  // namespace
 }  // namespace rsm
