@@ -602,6 +602,118 @@ int rsm_ns_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_
                              uint32_t count, const rsm_nmt_params* nmt, const rsm_ns_query* queries,
                              const uint8_t* nids, uint32_t n, void* d_status, void* stream);
 
+/* ---- range proofs ------------------------------------------------------------------ */
+/* "These shares are leaves [start, end) of this row (or column), under this root": nmt's
+ * ProveRange / VerifyInclusion, and per touched row the share half of Celestia's
+ * ShareProof (the other half, the row roots under the data root, is "data root" above).
+ * An inclusion claim, not a completeness claim: the caller names the range, for either
+ * tree.  Vector and leaf namespaces as in "namespace proofs".
+ * Record, fixed stride rsm_range_record_bytes = 16 + (2L + 1) * node_len: the namespace
+ * record of kind RSM_NS_INCLUSION over [start, end) --
+ *   uint32 kind = 1 | uint32 start | uint32 end | uint32 n_nodes | n_nodes nodes | zeros up
+ *   to slot 2L | slot 2L zeros
+ * with the nodes and their order as "namespace proofs" derives them from (W, start, end)
+ * (never more than 2L); node_len = 32 with nmt == NULL (DefaultTree), else
+ * 2 * namespace_size + 32.  For an NMT range that is exactly a namespace's range the
+ * record is byte-identical to the one rsm_ns_proofs_dev writes. */
+typedef struct {
+    uint32_t square; /* square of a batch */
+    uint32_t axis;   /* RSM_AXIS_ROW / RSM_AXIS_COL */
+    uint32_t index;  /* row or column */
+    uint32_t start;  /* leaves [start, end) of it */
+    uint32_t end;
+} rsm_range_query;
+/* Bytes of one range proof record (0 for width 0 or a namespace size 0). */
+uint32_t rsm_range_record_bytes(uint32_t width, const rsm_nmt_params* nmt);
+/* n range proofs out of a node store.  Operands, alignment, the shares_cap rule, limits
+ * and asynchrony as rsm_ns_proofs_dev, except: there is no d_status and there are no
+ * nids; nmt == NULL is accepted and means a DefaultTree store (every width that store
+ * takes); `queries` (HOST memory, copied before the call returns, n <= 2^20) is validated
+ * before anything is enqueued, RSM_EINVAL naming the first query with square >= count,
+ * axis > 1, index >= width or not start < end <= width.  The call proves ranges of
+ * whatever the store holds: a tree whose status word (rsm_proof_nodes_dev) is non-zero
+ * still has every node, and its proofs fold to the root stored for it. */
+int rsm_range_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_t width, uint32_t share_size,
+                         uint32_t count, const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n,
+                         void* d_records, void* d_offsets, void* d_shares, uint64_t shares_cap, void* stream);
+/* Host restatements (merkle.cpp), any n_leaves >= 1: the record of leaves [start, end) of
+ * the vector `leaves` into record_out (rsm_range_record_bytes(n_leaves, ..)), the root
+ * into root_out (nullable).  RSM_EINVAL unless start < end <= n_leaves; RSM_ETREE where
+ * the tree fails, as rsm_nmt_tree_prove. */
+int rsm_default_tree_range_prove(const uint8_t* const* leaves, uint32_t n_leaves, uint32_t leaf_size, uint32_t start,
+                                 uint32_t end, uint8_t* record_out, uint8_t* root_out);
+int rsm_nmt_tree_range_prove(const rsm_nmt_params* params, uint32_t index, const uint8_t* const* leaves,
+                             uint32_t n_leaves, uint32_t leaf_size, uint32_t start, uint32_t end, uint8_t* record_out,
+                             uint8_t* root_out);
+/* Verification (host forms; the device forms follow): are `shares` [n_shares][share_size]
+ * leaves [start, end) of the tree of n_leaves leaves with root `root`, by `record`?  start
+ * and end are the CALLER's question.  *status, the first that applies:
+ * 1 RSM_PROOF_MALFORMED: n_shares != end - start; record kind != 1; the record's start or
+ *   end differ from the caller's; n_nodes differs from the count (n_leaves, start, end)
+ *   dictates.
+ * 2 RSM_PROOF_ORDER (NMT): a join has right.min < left.max.
+ * 3 RSM_PROOF_ROOT: the fold differs from the root (NMT: all of min || max || digest).
+ * 0 RSM_PROOF_OK.  There is no NAMESPACE or INCOMPLETE status.
+ * NMT leaf p takes the wrapper's namespace, so a range may cross square_size and hold
+ * several namespaces; ignore_max_namespace is honoured in every join.  The return value
+ * is an argument error only (RSM_EINVAL, also unless start < end <= n_leaves; RSM_ETREE
+ * for shares shorter than the namespace). */
+int rsm_default_tree_range_verify(uint32_t start, uint32_t end, const uint8_t* shares, uint32_t n_shares,
+                                  uint32_t share_size, uint32_t n_leaves, const uint8_t* record, const uint8_t* root,
+                                  uint32_t* status);
+int rsm_nmt_tree_range_verify(const rsm_nmt_params* params, uint32_t index, uint32_t start, uint32_t end,
+                              const uint8_t* shares, uint32_t n_shares, uint32_t share_size, uint32_t n_leaves,
+                              const uint8_t* record, const uint8_t* root, uint32_t* status);
+/* Device form: n range proofs in one launch, one wave per query, on exactly what
+ * rsm_range_proofs_dev writes.  d_records [n][rsm_range_record_bytes(width, nmt)] (any
+ * alignment), d_offsets n + 1 uint32 (4-byte aligned), d_shares (16-byte aligned,
+ * shares_total shares; NULL only with shares_total == 0), d_roots [count][2][width]
+ * [node_len] as the roots calls lay them out, d_status [n] uint32 (4-byte aligned).
+ * `queries` are HOST memory, validated as in rsm_range_proofs_dev before anything is
+ * enqueued and copied before the call returns; n <= 2^20.  d_status[i] receives the word
+ * the host form gives for query i's start and end with n_shares = d_offsets[i + 1] -
+ * d_offsets[i], after one device-only rule: if d_offsets[i] > d_offsets[i + 1] or
+ * d_offsets[i + 1] > shares_total the status is MALFORMED and nothing of that query's
+ * record or shares is read.
+ * The contract, as for the other verifiers:
+ *   Positions are bound.  start and end come from the query, host memory of the verifier;
+ *   the record's are only compared with them.  A valid proof of [a, b) presented for
+ *   [a + 1, b + 1), or for the same range of another vector, does not verify.
+ *   Counts, operand sides and every address come from (width, start, end) and the
+ *   offsets, never from what a record or a share holds.  Record bytes past the derived
+ *   nodes are never read, slot 2L included.
+ *   Writes.  Exactly one status word is written per query, and nothing else.
+ * No tree is built and no node store is needed.  NMT: 1 <= width <= 1024, namespace_size
+ * 1..32 (else RSM_EINVAL); DefaultTree (nmt == NULL): 1 <= width <= 2048 (64 KiB of LDS
+ * per wave at 2048); odd widths included; beyond: RSM_EUNSUPPORTED.  share_size a
+ * multiple of 64 (else RSM_ESHARESIZE) and, NMT, >= namespace_size (else RSM_ETREE).
+ * RSM_EINVAL also for NULL or misaligned operands and n > 2^20.  Checks in the order of
+ * rsm_ns_proofs_verify_dev.  n == 0 or count == 0 launches nothing.  Asynchronous on
+ * `stream`. */
+int rsm_range_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets, const void* d_shares,
+                                uint64_t shares_total, const void* d_roots, uint32_t width, uint32_t share_size,
+                                uint32_t count, const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n,
+                                void* d_status, void* stream);
+/* Chained form, with no root table: query i also takes root record i of d_root_records
+ * (stride rsm_data_root_record_bytes(width), as rsm_root_proofs_dev writes it for
+ * (square, axis, index)) and is compared with d_data_roots[square] (32 bytes).  Straight
+ * after rule 1 and before anything is hashed, a root record whose header differs from
+ * what (2 * width, axis * width + index) dictates is MALFORMED.  The range's folded root
+ * (NMT: min || max || digest) is then hashed as that leaf of the data-root tree and folded
+ * through the root record: RSM_PROOF_ORDER (NMT, the range fold), RSM_PROOF_ROOT or
+ * RSM_PROOF_OK.  Everything else as rsm_range_proofs_verify_dev. */
+int rsm_range_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets,
+                                          const void* d_shares, uint64_t shares_total, const void* d_root_records,
+                                          const void* d_data_roots, uint32_t width, uint32_t share_size, uint32_t count,
+                                          const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n,
+                                          void* d_status, void* stream);
+/* Host only: ODS shares [start, end) in row-major order of the k x k original square of
+ * `square` as one row query per touched row (share i: row i / k, column i % k, all below
+ * k) into queries_out[0 .. *n_out), at most k of them -- the row ranges of a ShareProof.
+ * RSM_EINVAL unless start < end <= k * k, 1 <= k <= 32768 and the operands are non-NULL. */
+int rsm_share_range_queries(uint32_t k, uint32_t square, uint32_t start, uint32_t end,
+                            rsm_range_query* queries_out /* [k] */, uint32_t* n_out);
+
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */
 int rsm_eds_compute(rsm_ctx* ctx, const uint8_t* const* data, const uint32_t* lens, uint64_t n,
@@ -665,6 +777,19 @@ int rsm_eds_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm
 int rsm_eds_namespace_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, int axis, const uint32_t* indices,
                              uint32_t n, const uint8_t* nid, uint8_t* records_out, uint32_t* offsets_out,
                              uint8_t* shares_out, uint64_t shares_cap);
+
+/* Range proofs ("range proofs" above) of n queries (square = 0) of this square: n records
+ * of rsm_range_record_bytes(width, nmt) into records_out, offsets_out[n + 1] and the
+ * packed shares into shares_out (nullable, room for shares_cap shares) as
+ * rsm_range_proofs_dev writes them -- query i's shares only where offsets_out[i + 1] <=
+ * shares_cap.  tree_fn / user as rsm_eds_proofs (the DefaultTree and the NMT; any other
+ * plugin RSM_EUNSUPPORTED).  RSM_EINVAL for a query out of range, RSM_ETREE for a vector
+ * that is incomplete or whose tree fails.  With a context and a complete square of a
+ * width the device trees take, the cached node store of rsm_eds_proofs is reused or built
+ * and one rsm_range_proofs_dev call answers; otherwise the host restatement runs per
+ * query.  Results never depend on the path. */
+int rsm_eds_range_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_range_query* queries, uint32_t n,
+                         uint8_t* records_out, uint32_t* offsets_out, uint8_t* shares_out, uint64_t shares_cap);
 
 /* Rebuilding a square from sampled shares: verifies n samples (square = 0; shares
  * [n][share size], records [n][rsm_proof_record_bytes(width, nmt)]) against the

@@ -43,6 +43,8 @@ __all__ = [
     "gather_vectors_dev", "byzantine_data_dev",
     "FRAUD_VALID", "FRAUD_TOOFEW", "FRAUD_SHARE", "FRAUD_CONSISTENT", "FraudVerdict", "fraud_proof_samples",
     "verify_fraud_proofs_dev", "BadEncodingProof",
+    "RangeQuery", "RangeProof", "ShareProof", "share_range_queries", "prove_ranges_dev", "verify_ranges_dev",
+    "verify_ranges_data_root_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -260,6 +262,20 @@ SIGNATURES = {
                                         ctypes.POINTER(_U32)]),
     "rsm_ns_proofs_verify_dev": (_I32, [_VP, _VP, _VP, _VP, _U64, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _VP,
                                         _U32, _VP, _VP]),
+    "rsm_range_record_bytes": (_U32, [_U32, ctypes.POINTER(NmtParams)]),
+    "rsm_range_proofs_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP, _U32, _VP, _VP, _VP, _U64,
+                                    _VP]),
+    "rsm_default_tree_range_prove": (_I32, [_VP, _U32, _U32, _U32, _U32, _VP, _VP]),
+    "rsm_nmt_tree_range_prove": (_I32, [ctypes.POINTER(NmtParams), _U32, _VP, _U32, _U32, _U32, _U32, _VP, _VP]),
+    "rsm_default_tree_range_verify": (_I32, [_U32, _U32, _VP, _U32, _U32, _U32, _VP, _VP, ctypes.POINTER(_U32)]),
+    "rsm_nmt_tree_range_verify": (_I32, [ctypes.POINTER(NmtParams), _U32, _U32, _U32, _VP, _U32, _U32, _U32, _VP, _VP,
+                                         ctypes.POINTER(_U32)]),
+    "rsm_range_proofs_verify_dev": (_I32, [_VP, _VP, _VP, _VP, _U64, _VP, _U32, _U32, _U32, ctypes.POINTER(NmtParams), _VP,
+                                           _U32, _VP, _VP]),
+    "rsm_range_proofs_verify_data_root_dev": (_I32, [_VP, _VP, _VP, _VP, _U64, _VP, _VP, _U32, _U32, _U32,
+                                                     ctypes.POINTER(NmtParams), _VP, _U32, _VP, _VP]),
+    "rsm_share_range_queries": (_I32, [_U32, _U32, _U32, _U32, _VP, ctypes.POINTER(_U32)]),
+    "rsm_eds_range_proofs": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _U64]),
     "rsm_eds_namespace_proofs": (_I32, [_VP, _VP, _VP, _I32, _VP, _U32, _VP, _VP, _VP, _VP, _U64]),
     "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
     "rsm_data_root_record_bytes": (_U32, [_U32]),
@@ -1243,6 +1259,211 @@ def verify_namespaces_dev(records: "DeviceBuffer", offsets: "DeviceBuffer", shar
     return out
 
 
+# ---------------------------------------------------------------------------
+# Range proofs (include/rsmt2d_hip.h "range proofs")
+# ---------------------------------------------------------------------------
+class RangeQuery(ctypes.Structure):
+    """rsm_range_query: leaves [``start``, ``end``) of row (axis 0) / column (axis 1)
+    ``index`` of ``square``."""
+    _fields_ = [("square", ctypes.c_uint32), ("axis", ctypes.c_uint32), ("index", ctypes.c_uint32),
+                ("start", ctypes.c_uint32), ("end", ctypes.c_uint32)]
+
+
+class RangeProof:
+    """Shares ``start`` .. ``end - 1`` of a row or column with their proof under its root
+    (nmt's ProveRange; one row of Celestia's ShareProof).
+
+    ``nodes``: the range proof of [start, end) in nmt's ``Proof.Nodes`` order;
+    ``numLeaves``, ``nmt`` (None: DefaultTree), ``axis``, ``tree_index``: the tree."""
+
+    def __init__(self, start: int, end: int, nodes: List[bytes], shares: List[bytes], numLeaves: int,
+                 nmt: Optional[NmtParams] = None, axis: int = 0, tree_index: int = 0):
+        self.start, self.end, self.nodes, self.shares = start, end, nodes, shares
+        self.numLeaves, self.nmt, self.axis, self.tree_index = numLeaves, nmt, axis, tree_index
+
+    def record(self) -> bytes:
+        """The range proof record (include/rsmt2d_hip.h): u32 kind = 1 | start | end |
+        n_nodes | the nodes | zeros up to and including slot 2L."""
+        nl = 2 * int(self.nmt.namespace_size) + 32 if self.nmt is not None else 32
+        levels = (self.numLeaves - 1).bit_length()
+        if len(self.nodes) > 2 * levels or any(len(nd) != nl for nd in self.nodes):
+            raise RSMError(RSM_EINVAL, "proof nodes do not fit the tree's record")
+        head = b"".join(int(v).to_bytes(4, "little") for v in (NS_INCLUSION, self.start, self.end, len(self.nodes)))
+        body = b"".join(self.nodes)
+        return head + body + bytes((2 * levels + 1) * nl - len(body))
+
+    def verify(self, root: bytes) -> int:
+        """The RSM_PROOF_* status of ``shares`` as leaves [start, end) under the committed
+        ``root`` (rsm_default_tree_range_verify / rsm_nmt_tree_range_verify)."""
+        S = len(self.shares[0]) if self.shares else 0
+        if any(len(sh) != S for sh in self.shares):
+            raise RSMError(RSM_EINVAL, "shares of different sizes")
+        st, L = ctypes.c_uint32(0), library()
+        flat = b"".join(self.shares)
+        if self.nmt is None:
+            _check(L.rsm_default_tree_range_verify(self.start, self.end, flat, len(self.shares), S, self.numLeaves,
+                                                   self.record(), bytes(root), ctypes.byref(st)))
+        else:
+            _check(L.rsm_nmt_tree_range_verify(ctypes.byref(self.nmt), self.tree_index, self.start, self.end, flat,
+                                               len(self.shares), S, self.numLeaves, self.record(), bytes(root),
+                                               ctypes.byref(st)))
+        return int(st.value)
+
+
+def _parse_range_records(rec: bytes, offsets, shares: bytes, queries, width: int, S: int,
+                         nmt: Optional[NmtParams]) -> List[RangeProof]:
+    """RangeProof objects from n records, the n + 1 offsets and the packed shares; queries:
+    (axis, index, start, end)."""
+    nl = 2 * int(nmt.namespace_size) + 32 if nmt is not None else 32
+    rb = 16 + (2 * (width - 1).bit_length() + 1) * nl
+    out = []
+    for i, (axis, index, start, end) in enumerate(queries):
+        r = rec[i * rb:(i + 1) * rb]
+        n_nodes = int.from_bytes(r[12:16], "little")
+        nodes = [r[16 + j * nl: 16 + (j + 1) * nl] for j in range(n_nodes)]
+        sh = [shares[p * S:(p + 1) * S] for p in range(int(offsets[i]), int(offsets[i + 1]))]
+        out.append(RangeProof(start, end, nodes, sh, width, nmt, axis, index))
+    return out
+
+
+def share_range_queries(k: int, start: int, end: int, square: int = 0) -> List[tuple]:
+    """ODS shares [start, end) in row-major order of the k x k original square as one
+    ``(square, Row, row, first, last + 1)`` query per touched row (rsm_share_range_queries)."""
+    out = (RangeQuery * max(k, 1))()
+    n = ctypes.c_uint32(0)
+    _check(library().rsm_share_range_queries(k, square, start, end, out, ctypes.byref(n)))
+    return [(q.square, q.axis, q.index, q.start, q.end) for q in out[:n.value]]
+
+
+def prove_ranges_dev(buf: "DeviceBuffer", width: int, share_size: int, queries: Sequence[tuple],
+                     nmt: Optional[NmtParams] = None, count: int = 1) -> List[RangeProof]:
+    """Range proofs of ``(square, axis, index, start, end)`` queries of ``count`` complete
+    device-resident [width][width][share_size] squares in ``buf``: one node-store build
+    (rsm_proof_nodes_dev) and one rsm_range_proofs_dev (the share total is known up front)."""
+    import numpy as np
+    L, ctx, n = library(), buf.ctx, len(queries)
+    p = _nmt_ref(nmt)
+    nbytes = int(L.rsm_proof_nodes_bytes(width, p, count))
+    if nbytes == 0:
+        raise RSMError(RSM_EUNSUPPORTED, f"device proofs: {count} squares of width {width} not supported")
+    if n == 0:
+        return []
+    rb = int(L.rsm_range_record_bytes(width, p))
+    total = sum(max(int(q[4]) - int(q[3]), 0) for q in queries)
+    bufs = [DeviceBuffer(nbytes), DeviceBuffer(n * rb), DeviceBuffer((n + 1) * 4), DeviceBuffer(max(total * share_size, 16))]
+    nodes, recs, offs, shs = bufs
+    try:
+        _check(L.rsm_proof_nodes_dev(ctx, buf.ptr, width, share_size, count, p, nodes.ptr, None, None, None))
+        _check(L.rsm_range_proofs_dev(ctx, nodes.ptr, buf.ptr, width, share_size, count, p, _records(RangeQuery, queries), n,
+                                      recs.ptr, offs.ptr, shs.ptr, total, None))
+        _check(L.rsm_sync(ctx))
+        offsets = offs.download((n + 1) * 4).view(np.uint32).copy()
+        sh = shs.download(max(total * share_size, 16)).tobytes()
+        rec = recs.download(n * rb).tobytes()
+    finally:
+        for b in bufs:
+            b.free()
+    return _parse_range_records(rec, offsets, sh, [q[1:] for q in queries], width, share_size, nmt)
+
+
+def _verify_ranges(call, records, offsets, shares, shares_total, against, width, share_size, queries, nmt, count):
+    import numpy as np
+    L, ctx, n = library(), records.ctx, len(queries)
+    out = np.zeros(n, np.uint32)
+    if n == 0:
+        return out
+    st = DeviceBuffer(n * 4)
+    try:
+        _check(getattr(L, call)(ctx, records.ptr, offsets.ptr, shares.ptr if shares is not None else None, shares_total,
+                                *[b.ptr for b in against], width, share_size, count, _nmt_ref(nmt),
+                                _records(RangeQuery, queries), n, st.ptr, None))
+        _check(L.rsm_sync(ctx))
+        out[:] = st.download(n * 4).view(np.uint32)
+    finally:
+        st.free()
+    return out
+
+
+def verify_ranges_dev(records: "DeviceBuffer", offsets: "DeviceBuffer", shares: Optional["DeviceBuffer"],
+                      shares_total: int, roots: "DeviceBuffer", width: int, share_size: int, queries: Sequence[tuple],
+                      nmt: Optional[NmtParams] = None, count: int = 1):
+    """Status words (RSM_PROOF_*) of ``(square, axis, index, start, end)`` queries whose
+    records, offsets and packed shares are device-resident as rsm_range_proofs_dev writes
+    them, against ``roots`` ([count][2][width][root bytes]): one
+    rsm_range_proofs_verify_dev launch, one wave per query.  0 = these shares are leaves
+    [start, end) of that vector."""
+    return _verify_ranges("rsm_range_proofs_verify_dev", records, offsets, shares, shares_total, [roots], width, share_size,
+                          queries, nmt, count)
+
+
+def verify_ranges_data_root_dev(records: "DeviceBuffer", offsets: "DeviceBuffer", shares: Optional["DeviceBuffer"],
+                                shares_total: int, root_records: "DeviceBuffer", data_roots: "DeviceBuffer", width: int,
+                                share_size: int, queries: Sequence[tuple], nmt: Optional[NmtParams] = None, count: int = 1):
+    """The same all the way to each square's data root, with no root table: query i also
+    takes root proof record i of ``root_records`` (as rsm_root_proofs_dev writes them) and
+    ``data_roots`` [count][32]: one rsm_range_proofs_verify_data_root_dev launch."""
+    return _verify_ranges("rsm_range_proofs_verify_data_root_dev", records, offsets, shares, shares_total,
+                          [root_records, data_roots], width, share_size, queries, nmt, count)
+
+
+class ShareProof:
+    """ODS shares [start, end) of a square under its data root (Celestia's ShareProof): per
+    touched row a ``RangeProof`` and the ``RootProof`` of that row's root; ``row_roots``:
+    the row roots the range proofs fold to."""
+
+    def __init__(self, start: int, end: int, rows: List[RangeProof], root_proofs: List[RootProof], row_roots: List[bytes]):
+        self.start, self.end, self.rows, self.root_proofs, self.row_roots = start, end, rows, root_proofs, row_roots
+
+    def shares(self) -> List[bytes]:
+        return [sh for pr in self.rows for sh in pr.shares]
+
+    def statuses(self, dataRoot: bytes, device: Optional[int] = 0) -> List[int]:
+        """One RSM_PROOF_* status per row for the chained check against ``dataRoot``: one
+        rsm_range_proofs_verify_data_root_dev call on GPU ``device``; ``device=None``
+        verifies each range against its row root and that root under ``dataRoot`` on the
+        host.  Results never depend on the path."""
+        import numpy as np
+        if not self.rows or len(self.rows) != len(self.root_proofs) or len(self.rows) != len(self.row_roots):
+            raise RSMError(RSM_EINVAL, "a ShareProof has one range proof, root proof and row root per row")
+        if device is None:
+            out = []
+            for pr, rp, root in zip(self.rows, self.root_proofs, self.row_roots):
+                st = pr.verify(root)
+                out.append(st if st != RSM_PROOF_OK else RootProof(rp.nodes, rp.right_mask, pr.axis, pr.tree_index,
+                                                                    pr.numLeaves).verify(root, dataRoot))
+            return out
+        w, nmt = self.rows[0].numLeaves, self.rows[0].nmt
+        sizes = {len(sh) for pr in self.rows for sh in pr.shares}
+        if len(sizes) > 1 or any(pr.numLeaves != w for pr in self.rows):
+            raise RSMError(RSM_EINVAL, "shares of different sizes or rows of different squares")
+        S = sizes.pop() if sizes else 64
+        offsets = np.cumsum([0] + [len(pr.shares) for pr in self.rows]).astype(np.uint32)
+        total = int(offsets[-1])
+        recs = b"".join(pr.record() for pr in self.rows)
+        rrecs = b"".join(RootProof(rp.nodes, rp.right_mask, rp.axis, rp.index, w).record() for rp in self.root_proofs)
+        bufs = [DeviceBuffer(len(recs), device), DeviceBuffer(offsets.nbytes, device), DeviceBuffer(max(total * S, 16), device),
+                DeviceBuffer(len(rrecs), device), DeviceBuffer(32, device)]
+        try:
+            bufs[0].upload(np.frombuffer(recs, np.uint8))
+            bufs[1].upload(offsets.view(np.uint8))
+            if total:
+                bufs[2].upload(np.frombuffer(b"".join(self.shares()), np.uint8))
+            bufs[3].upload(np.frombuffer(rrecs, np.uint8))
+            bufs[4].upload(np.frombuffer(bytes(dataRoot), np.uint8))
+            st = verify_ranges_data_root_dev(bufs[0], bufs[1], bufs[2], total, bufs[3], bufs[4], w, S,
+                                             [(0, pr.axis, pr.tree_index, pr.start, pr.end) for pr in self.rows], nmt)
+            return [int(x) for x in st]
+        finally:
+            for b in bufs:
+                b.free()
+
+    def Validate(self, dataRoot: bytes, device: Optional[int] = 0) -> bool:
+        """True iff every row's chained check against ``dataRoot`` is RSM_PROOF_OK."""
+        if len(dataRoot) != 32:
+            raise RSMError(RSM_EINVAL, "a data root of 32 bytes is needed")
+        return all(st == RSM_PROOF_OK for st in self.statuses(dataRoot, device))
+
+
 def verify_namespace_data(row_roots: Sequence[bytes], nid: bytes, data: Sequence[tuple], nmt: NmtParams, width: int,
                           device: Optional[int] = 0) -> List[int]:
     """The client side of ``ExtendedDataSquare.NamespaceData``: one RSM_PROOF_* status per
@@ -1493,6 +1714,35 @@ class ExtendedDataSquare:
         sh = ctypes.create_string_buffer(max(cap * S, 1))
         _check(L.rsm_eds_namespace_proofs(self._h, fn, user, axis, idx, n, bytes(nid), rec, offs, sh, cap))
         return _parse_ns_records(rec.raw, list(offs), sh.raw, indices, w, S, nmt)
+
+    # --- range proofs (rsm_eds_range_proofs) ---
+    def RangeProofs(self, queries: Sequence[tuple]) -> List["RangeProof"]:
+        """Leaves [start, end) of row / column ``index`` for each ``(axis, index, start,
+        end)`` query, with their range proof under that vector's root (nmt's ProveRange;
+        verify with ``RangeProof.verify``).  Trees and paths as ``Proofs``."""
+        tf = self._tree_fn
+        if not (tf is None or tf is NewDefaultTree or isinstance(tf, ErasuredNamespacedMerkleTreeConstructor)):
+            raise RSMError(RSM_EUNSUPPORTED, "range proofs are built for the DefaultTree and the NMT only")
+        keep, fn, user = _tree_callback(tf)
+        nmt = tf.params if isinstance(tf, ErasuredNamespacedMerkleTreeConstructor) else None
+        L, w, S, n = library(), self.Width(), self.shareSize, len(queries)
+        arr = _records(RangeQuery, [(0, a, i, s, e) for (a, i, s, e) in queries])
+        rb = int(L.rsm_range_record_bytes(max(w, 1), _nmt_ref(nmt)))
+        cap = sum(max(int(e) - int(s), 0) for (_, _, s, e) in queries)
+        rec = ctypes.create_string_buffer(max(n * rb, 1))
+        offs = (ctypes.c_uint32 * (n + 1))()
+        sh = ctypes.create_string_buffer(max(cap * S, 1))
+        _check(L.rsm_eds_range_proofs(self._h, fn, user, arr, n, rec, offs, sh, cap))
+        return _parse_range_records(rec.raw, list(offs), sh.raw, queries, w, S, nmt)
+
+    def ShareProof(self, start: int, end: int) -> "ShareProof":
+        """ODS shares [start, end) (row-major in the original k x k square) with one
+        ``RangeProof`` per touched row and each row root's ``RootProof`` under DataRoot():
+        what a rollup or bridge checks against a block header (``.Validate(dataRoot)``)."""
+        rows = share_range_queries(self.originalDataWidth, start, end)
+        proofs = self.RangeProofs([q[1:] for q in rows])
+        roots = self.RowRoots()
+        return ShareProof(start, end, proofs, [self.RootProof(Row, q[2]) for q in rows], [roots[q[2]] for q in rows])
 
     def NamespaceData(self, nid: bytes) -> List[tuple]:
         """``(rowIdx, NamespaceProof)`` for every row whose proof for ``nid`` is not

@@ -27,7 +27,9 @@
 // nmt_proof_verify_data_root_kernel (the same lane, hashing the fold's node as a leaf of
 // the data-root tree and folding on to the square's data root: no root table) and
 // nmt_ns_verify_kernel (one wave per namespace proof: the leaves of its range, the fold of
-// its range proof in the wave's LDS, the completeness checks; any width up to 1024).
+// its range proof in the wave's LDS, the completeness checks; any width up to 1024) and
+// nmt_range_verify_kernel (the same wave for a range the caller names, an inclusion claim
+// with no completeness checks; also chained to the data root).
 // Namespace sizes up to 32 bytes (Celestia: 29), widths up to 1024 (LDS permitting).
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -833,6 +835,45 @@ __global__ __launch_bounds__(256) void nmt_proof_verify_kernel(const uint8_t* __
     status[t] = !ordered ? kProofOrder : (diff ? kProofRoot : kProofOk);
 }
 
+// The node's 2 ns + 32 bytes min || max || digest as zero-padded big-endian words: what the
+// data-root tree hashes as a leaf.  NS = 29: from compile-time positions; NS = 0: through
+// the lane's LDS message bytes mb (at least 128 for every namespace size), as hash_node
+// lays out a node.
+template <int NS>
+__device__ __forceinline__ void node_root_words(const Node& acc, uint32_t ns, uint8_t* mb, uint32_t (&B)[kRootWords]) {
+    if constexpr (NS == 0) {
+        uint32_t* mw = reinterpret_cast<uint32_t*>(mb);
+#pragma unroll
+        for (int i = 0; i < kRootWords; ++i) mw[i] = 0;
+#pragma unroll
+        for (int i = 0; i < (int)kMaxNs; ++i)
+            if (i < (int)ns) {
+                mb[i] = be_byte(acc.mn, i);
+                mb[(int)ns + i] = be_byte(acc.mx, i);
+            }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) mb[2 * (int)ns + i] = be_byte(acc.d, i);
+#pragma unroll
+        for (int i = 0; i < kRootWords; ++i) B[i] = __builtin_bswap32(mw[i]);
+    } else {
+        WNode<NS> x;
+#pragma unroll
+        for (int q = 0; q < (int)kNsWords; ++q) x.mn[q] = acc.mn[q], x.mx[q] = acc.mx[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x.d[q] = acc.d[q];
+        constexpr int NLc = 2 * NS + 32;
+        sfor_n<kRootWords>([&](auto Ic) {
+            constexpr int i = decltype(Ic)::value;
+            uint32_t v = 0;
+            if constexpr (4 * i < NLc) v |= node_byte<NS, 4 * i>(x) << 24;
+            if constexpr (4 * i + 1 < NLc) v |= node_byte<NS, 4 * i + 1>(x) << 16;
+            if constexpr (4 * i + 2 < NLc) v |= node_byte<NS, 4 * i + 2>(x) << 8;
+            if constexpr (4 * i + 3 < NLc) v |= node_byte<NS, 4 * i + 3>(x);
+            B[i] = v;
+        });
+    }
+}
+
 // Chained verification (rsm_kernels.hpp "data root"), NMT: the same lane, with no root
 // table.  Both headers -- the share record's against (W, pos), the root record's against
 // (2W, axis W + index) -- are compared before anything is hashed.  The share fold's node
@@ -869,37 +910,7 @@ __global__ __launch_bounds__(256) void nmt_proof_verify_data_root_kernel(
         return;
     }
     uint32_t B[kRootWords], g[8];  // the candidate root's bytes as big-endian words
-    if constexpr (NS == 0) {
-        uint32_t* mw = reinterpret_cast<uint32_t*>(mb);
-#pragma unroll
-        for (int i = 0; i < kRootWords; ++i) mw[i] = 0;
-#pragma unroll
-        for (int i = 0; i < (int)kMaxNs; ++i)
-            if (i < (int)ns) {
-                mb[i] = be_byte(acc.mn, i);
-                mb[(int)ns + i] = be_byte(acc.mx, i);
-            }
-#pragma unroll
-        for (int i = 0; i < 32; ++i) mb[2 * (int)ns + i] = be_byte(acc.d, i);
-#pragma unroll
-        for (int i = 0; i < kRootWords; ++i) B[i] = __builtin_bswap32(mw[i]);
-    } else {
-        WNode<NS> x;
-#pragma unroll
-        for (int q = 0; q < (int)kNsWords; ++q) x.mn[q] = acc.mn[q], x.mx[q] = acc.mx[q];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) x.d[q] = acc.d[q];
-        constexpr int NLc = 2 * NS + 32;
-        sfor_n<kRootWords>([&](auto Ic) {
-            constexpr int i = decltype(Ic)::value;
-            uint32_t v = 0;
-            if constexpr (4 * i < NLc) v |= node_byte<NS, 4 * i>(x) << 24;
-            if constexpr (4 * i + 1 < NLc) v |= node_byte<NS, 4 * i + 1>(x) << 16;
-            if constexpr (4 * i + 2 < NLc) v |= node_byte<NS, 4 * i + 2>(x) << 8;
-            if constexpr (4 * i + 3 < NLc) v |= node_byte<NS, 4 * i + 3>(x);
-            B[i] = v;
-        });
-    }
+    node_root_words<NS>(acc, ns, mb, B);
     root_leaf_hash(B, NL, g);
     status[t] = data_root_matches(g, rrec, n2, mask2, data_roots + (uint64_t)sm.square * 32u) ? kProofOk : kProofRoot;
 }
@@ -927,77 +938,50 @@ __global__ __launch_bounds__(256) void nmt_proof_verify_data_root_kernel(
 // Counts, sides and every address come from (W, start, end) and the offsets, after the
 // header passed the MALFORMED checks; nothing of a record past its derived nodes (and, for
 // ABSENCE, the leaf slot) is read.
+
+// The leaves of a range (the namespace and the range verifier): lane j hashes shares j,
+// j + 64, .. of the n_shares at share o0 into entries start + j, ..; the leaf's namespace
+// is the wrapper's (quadrant 0: the share's own).  Returns whether one of the lane's own
+// leaves carries a namespace other than nid (nid == nullptr: nothing is compared).
+// Every lane hashes in every pass, here and in the fold: past the pass's last leaf (node)
+// a lane repeats leaf i0 + lane % rem and stores it to the spare entry (a wave with few
+// lanes active runs its SHA rounds 2-3.5x slower per compression: kernels_sha.hip; the
+// store keeps the compiler from shrinking the hash to the owning lanes).
 template <int NS>
-__device__ __forceinline__ uint32_t ns_verify_query(const uint8_t* __restrict__ rec, const uint32_t* __restrict__ offsets,
-                                                    const uint8_t* __restrict__ shares, uint64_t shares_total,
-                                                    const uint8_t* __restrict__ roots, uint32_t W, uint32_t S, uint32_t ns,
-                                                    uint32_t k, bool ig, const NsQuery& qu, uint32_t lane,
-                                                    uint32_t* __restrict__ row, uint8_t* __restrict__ mb) {
-    uint32_t* const spare = row + (size_t)W * kNodeWords;  // entry W: what lanes past a pass's last node store
-    const uint32_t o0 = __builtin_amdgcn_readfirstlane(offsets[0]), o1 = __builtin_amdgcn_readfirstlane(offsets[1]);
-    if (o0 > o1 || o1 > shares_total) return kProofMalformed;  // nothing of the record or the shares is read
-    const uint32_t n_shares = o1 - o0, L = proof_levels(W), NL = 2u * ns + 32u;
-    const uint32_t kind = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec)),
-                   start = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 4)),
-                   end = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 8)),
-                   n_nodes = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 12));
-    Node rt;
-    node_from_bytes<NS>(roots + (((uint64_t)qu.square * 2u + qu.axis) * W + qu.index) * NL, ns, rt);
-    // 1. the header against what (W, start, end) dictates
-    if (kind == kNsEmpty) {
-        if (start | end | n_nodes | n_shares) return kProofMalformed;
-        return !ns_less(qu.nid, rt.mn) && !ns_less(rt.mx, qu.nid) ? kProofIncomplete : kProofOk;
-    }
-    if (kind == kNsInclusion) {
-        if (!(start < end && end <= W) || n_shares != end - start) return kProofMalformed;
-    } else if (kind == kNsAbsence) {
-        if (start >= W || end != start + 1u || n_shares != 0u) return kProofMalformed;
-    } else {
-        return kProofMalformed;  // kNsTree among them
-    }
-    uint32_t n_left = 0;
-    const uint32_t nn = ns_range_nodes(W, start, end, &n_left);
-    if (n_nodes != nn) return kProofMalformed;
-    // 2. the leaves carry nid / the absence leaf is one leaf above nid
+__device__ __forceinline__ bool range_leaves(const uint8_t* __restrict__ shares, uint32_t o0, uint32_t n_shares, uint32_t S,
+                                             uint32_t ns, uint32_t k, uint32_t index, uint32_t start, const uint32_t* nid,
+                                             uint32_t lane, uint32_t* __restrict__ row, uint32_t* __restrict__ spare) {
     bool flag = false;
-    if (kind == kNsInclusion) {
-        // Every lane hashes in every pass, here and in the fold: past the pass's last leaf
-        // (node) a lane repeats leaf i0 + lane % rem and stores it to the spare entry (a
-        // wave with few lanes active runs its SHA rounds 2-3.5x slower per compression:
-        // kernels_sha.hip; the store keeps the compiler from shrinking the hash to the
-        // owning lanes).
-        for (uint32_t i0 = 0; i0 < n_shares; i0 += 64u) {
-            const uint32_t rem = n_shares - i0;
-            const bool own = lane < rem;
-            const uint32_t i = i0 + (own ? lane : lane % rem);
-            const uint8_t* sp = shares + ((uint64_t)o0 + i) * S;
-            const bool q0 = qu.index < k && start + i < k;
-            Node lf;
-            if constexpr (NS == 29) verify_leaf29(sp, S, q0, lf);
-            else verify_leaf(sp, S, ns, q0, lf);
+    for (uint32_t i0 = 0; i0 < n_shares; i0 += 64u) {
+        const uint32_t rem = n_shares - i0;
+        const bool own = lane < rem;
+        const uint32_t i = i0 + (own ? lane : lane % rem);
+        const uint8_t* sp = shares + ((uint64_t)o0 + i) * S;
+        const bool q0 = index < k && start + i < k;
+        Node lf;
+        if constexpr (NS == 29) verify_leaf29(sp, S, q0, lf);
+        else verify_leaf(sp, S, ns, q0, lf);
+        if (nid) {
             bool differs = false;
 #pragma unroll
-            for (int w = 0; w < (int)kNsWords; ++w) differs |= lf.mn[w] != qu.nid[w];
+            for (int w = 0; w < (int)kNsWords; ++w) differs |= lf.mn[w] != nid[w];
             flag |= own && differs;
-            lds_store(own ? row + (size_t)(start + i) * kNodeWords : spare, lf);
         }
-    } else {
-        Node lf;
-        node_from_bytes<NS>(rec + 16u + 2u * L * NL, ns, lf);
-#pragma unroll
-        for (int w = 0; w < (int)kNsWords; ++w) flag |= lf.mn[w] != lf.mx[w];
-        flag |= !ns_less(qu.nid, lf.mn);
-        if (lane == 0) lds_store(row + (size_t)start * kNodeWords, lf);
+        lds_store(own ? row + (size_t)(start + i) * kNodeWords : spare, lf);
     }
-    if (__ballot(flag)) return kProofNamespace;
-    // 3. nothing of nid lies under a proof node (nn <= 2 L < 64)
-    if (lane < nn) {
-        Node nd;
-        node_from_bytes<NS>(rec + 16u + lane * NL, ns, nd);
-        flag = lane < n_left ? !ns_less(nd.mx, qu.nid) : !ns_less(qu.nid, nd.mn);
-    }
-    if (__ballot(flag)) return kProofIncomplete;
-    // 4, 5. the fold
+    return flag;
+}
+
+// The fold of a range whose level-0 entries start .. end - 1 are written (the "fold" step
+// above), the proof nodes taken from rec + 16; the root is entry 0 when it returns.
+// Returns whether one of the lane's own joins had unordered siblings.
+template <int NS>
+__device__ __forceinline__ bool range_fold(const uint8_t* __restrict__ rec, uint32_t W, uint32_t start, uint32_t end,
+                                           uint32_t n_left, uint32_t ns, bool ig, uint32_t lane, uint32_t* __restrict__ row,
+                                           uint8_t* __restrict__ mb) {
+    uint32_t* const spare = row + (size_t)W * kNodeWords;
+    const uint32_t L = proof_levels(W), NL = 2u * ns + 32u;
+    bool flag = false;
     auto wave_sync = [] {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1063,7 +1047,62 @@ __device__ __forceinline__ uint32_t ns_verify_query(const uint8_t* __restrict__ 
         last >>= 1;
     }
     wave_sync();
-    if (__ballot(flag)) return kProofOrder;
+    return flag;
+}
+
+template <int NS>
+__device__ __forceinline__ uint32_t ns_verify_query(const uint8_t* __restrict__ rec, const uint32_t* __restrict__ offsets,
+                                                    const uint8_t* __restrict__ shares, uint64_t shares_total,
+                                                    const uint8_t* __restrict__ roots, uint32_t W, uint32_t S, uint32_t ns,
+                                                    uint32_t k, bool ig, const NsQuery& qu, uint32_t lane,
+                                                    uint32_t* __restrict__ row, uint8_t* __restrict__ mb) {
+    uint32_t* const spare = row + (size_t)W * kNodeWords;  // entry W: what lanes past a pass's last node store
+    const uint32_t o0 = __builtin_amdgcn_readfirstlane(offsets[0]), o1 = __builtin_amdgcn_readfirstlane(offsets[1]);
+    if (o0 > o1 || o1 > shares_total) return kProofMalformed;  // nothing of the record or the shares is read
+    const uint32_t n_shares = o1 - o0, L = proof_levels(W), NL = 2u * ns + 32u;
+    const uint32_t kind = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec)),
+                   start = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 4)),
+                   end = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 8)),
+                   n_nodes = __builtin_amdgcn_readfirstlane(ld_any<uint32_t>(rec + 12));
+    Node rt;
+    node_from_bytes<NS>(roots + (((uint64_t)qu.square * 2u + qu.axis) * W + qu.index) * NL, ns, rt);
+    // 1. the header against what (W, start, end) dictates
+    if (kind == kNsEmpty) {
+        if (start | end | n_nodes | n_shares) return kProofMalformed;
+        return !ns_less(qu.nid, rt.mn) && !ns_less(rt.mx, qu.nid) ? kProofIncomplete : kProofOk;
+    }
+    if (kind == kNsInclusion) {
+        if (!(start < end && end <= W) || n_shares != end - start) return kProofMalformed;
+    } else if (kind == kNsAbsence) {
+        if (start >= W || end != start + 1u || n_shares != 0u) return kProofMalformed;
+    } else {
+        return kProofMalformed;  // kNsTree among them
+    }
+    uint32_t n_left = 0;
+    const uint32_t nn = ns_range_nodes(W, start, end, &n_left);
+    if (n_nodes != nn) return kProofMalformed;
+    // 2. the leaves carry nid / the absence leaf is one leaf above nid
+    bool flag = false;
+    if (kind == kNsInclusion) {
+        flag = range_leaves<NS>(shares, o0, n_shares, S, ns, k, qu.index, start, qu.nid, lane, row, spare);
+    } else {
+        Node lf;
+        node_from_bytes<NS>(rec + 16u + 2u * L * NL, ns, lf);
+#pragma unroll
+        for (int w = 0; w < (int)kNsWords; ++w) flag |= lf.mn[w] != lf.mx[w];
+        flag |= !ns_less(qu.nid, lf.mn);
+        if (lane == 0) lds_store(row + (size_t)start * kNodeWords, lf);
+    }
+    if (__ballot(flag)) return kProofNamespace;
+    // 3. nothing of nid lies under a proof node (nn <= 2 L < 64)
+    if (lane < nn) {
+        Node nd;
+        node_from_bytes<NS>(rec + 16u + lane * NL, ns, nd);
+        flag = lane < n_left ? !ns_less(nd.mx, qu.nid) : !ns_less(qu.nid, nd.mn);
+    }
+    if (__ballot(flag)) return kProofIncomplete;
+    // 4, 5. the fold
+    if (__ballot(range_fold<NS>(rec, W, start, end, n_left, ns, ig, lane, row, mb))) return kProofOrder;
     Node acc;
     lds_node(row, acc);
     uint32_t diff = 0;
@@ -1090,6 +1129,79 @@ __global__ __launch_bounds__(256) void nmt_ns_verify_kernel(const uint8_t* __res
     const NsQuery qu = queries[q];
     const uint32_t st = ns_verify_query<NS>(records + (uint64_t)q * record_bytes, offsets + q, shares, shares_total, roots, W,
                                             S, ns, k, ignore_max != 0, qu, lane, row, mb);
+    if (lane == 0) status[q] = st;
+}
+
+// Range proof verification (rsm_kernels.hpp "range proofs"): the namespace verifier's wave
+// with the claim bound to the caller's question instead of a namespace.  [start, end) is the
+// QUERY's (host-validated: start < end <= W); the record's header is only compared with it
+// and with the node count it dictates, so leaves, grafts and joins are addressed from the
+// query and the offsets alone.  The leaves take the wrapper's namespace position by
+// position (a range may cross square_size and hold several namespaces); there is no
+// NAMESPACE or INCOMPLETE step.  CHAINED: no root table -- root record rrec is checked
+// against (2W, axis W + index) with the other headers, before anything is hashed; the
+// fold's root is then hashed as that leaf of the data-root tree (every lane the same
+// work), folded on and compared with the square's data root dr.
+template <int NS, bool CHAINED>
+__device__ __forceinline__ uint32_t range_verify_query(const uint8_t* __restrict__ rec, const uint32_t* __restrict__ offsets,
+                                                       const uint8_t* __restrict__ shares, uint64_t shares_total,
+                                                       const uint8_t* __restrict__ root, const uint8_t* __restrict__ rrec,
+                                                       const uint8_t* __restrict__ dr, uint32_t W, uint32_t S, uint32_t ns,
+                                                       uint32_t k, bool ig, const RangeQuery& qu, uint32_t lane,
+                                                       uint32_t* __restrict__ row, uint8_t* __restrict__ mb) {
+    uint32_t* const spare = row + (size_t)W * kNodeWords;
+    const uint32_t o0 = __builtin_amdgcn_readfirstlane(offsets[0]), o1 = __builtin_amdgcn_readfirstlane(offsets[1]);
+    if (o0 > o1 || o1 > shares_total) return kProofMalformed;  // nothing of the record or the shares is read
+    const uint32_t start = __builtin_amdgcn_readfirstlane(qu.start), end = __builtin_amdgcn_readfirstlane(qu.end);
+    const uint32_t NL = 2u * ns + 32u;
+    if (o1 - o0 != end - start || ld_any<uint32_t>(rec) != kNsInclusion || ld_any<uint32_t>(rec + 4) != start ||
+        ld_any<uint32_t>(rec + 8) != end)
+        return kProofMalformed;
+    uint32_t n_left = 0;
+    if (ld_any<uint32_t>(rec + 12) != ns_range_nodes(W, start, end, &n_left)) return kProofMalformed;
+    uint32_t n2 = 0, mask2 = 0;
+    if constexpr (CHAINED) {
+        n2 = proof_shape(2u * W, qu.axis * W + qu.index, &mask2);
+        if (ld_any<uint32_t>(rrec) != n2 || ld_any<uint32_t>(rrec + 4) != mask2) return kProofMalformed;
+    }
+    range_leaves<NS>(shares, o0, end - start, S, ns, k, qu.index, start, nullptr, lane, row, spare);
+    if (__ballot(range_fold<NS>(rec, W, start, end, n_left, ns, ig, lane, row, mb))) return kProofOrder;
+    Node acc;
+    lds_node(row, acc);
+    if constexpr (CHAINED) {
+        uint32_t B[kRootWords], g[8];  // the candidate root's bytes as big-endian words
+        node_root_words<NS>(acc, ns, mb, B);
+        root_leaf_hash(B, NL, g);
+        return data_root_matches(g, rrec, n2, mask2, dr) ? kProofOk : kProofRoot;
+    } else {
+        Node rt;
+        node_from_bytes<NS>(root, ns, rt);
+        uint32_t diff = 0;
+#pragma unroll
+        for (int w = 0; w < (int)kNsWords; ++w) diff |= (acc.mn[w] ^ rt.mn[w]) | (acc.mx[w] ^ rt.mx[w]) | (acc.d[w] ^ rt.d[w]);
+        return diff ? kProofRoot : kProofOk;
+    }
+}
+
+template <int NS, bool CHAINED>
+__global__ __launch_bounds__(256) void nmt_range_verify_kernel(
+    const uint8_t* __restrict__ records, const uint32_t* __restrict__ offsets, const uint8_t* __restrict__ shares,
+    uint64_t shares_total, const uint8_t* __restrict__ roots, const uint8_t* __restrict__ root_records,
+    const uint8_t* __restrict__ data_roots, uint32_t W, uint32_t S, uint32_t ns, uint32_t k, uint32_t ignore_max,
+    const RangeQuery* __restrict__ queries, uint32_t n, uint32_t record_bytes, uint32_t wave_words,
+    uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // per wave, as nmt_ns_verify_kernel
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * (blockDim.x >> 6) + wv;
+    if (q >= n) return;
+    uint32_t* const row = lds + (size_t)wv * wave_words;
+    uint8_t* const mb = reinterpret_cast<uint8_t*>(row + (size_t)(W + 1u) * kNodeWords) + (NS == 0 ? lane * (64u * node_blocks(ns)) : 0u);
+    const RangeQuery qu = queries[q];
+    const uint8_t* root = CHAINED ? nullptr : roots + (((uint64_t)qu.square * 2u + qu.axis) * W + qu.index) * (2u * ns + 32u);
+    const uint8_t* rrec = CHAINED ? root_records + (uint64_t)q * (8u + proof_levels(2u * W) * 32u) : nullptr;
+    const uint8_t* dr = CHAINED ? data_roots + (uint64_t)qu.square * 32u : nullptr;
+    const uint32_t st = range_verify_query<NS, CHAINED>(records + (uint64_t)q * record_bytes, offsets + q, shares, shares_total,
+                                                        root, rrec, dr, W, S, ns, k, ignore_max != 0, qu, lane, row, mb);
     if (lane == 0) status[q] = st;
 }
 
@@ -1129,23 +1241,31 @@ bool nmt_ns_verify_supported(uint32_t W, uint32_t ns) { return W >= 1 && W <= kM
 
 // One wave per query, up to four waves per workgroup: the count that lets most waves share
 // a CU's LDS (W = 256: 24 KiB a wave, six waves per CU as two workgroups of three;
-// W = 1024, ns = 32: 112 KiB, one wave).
+// W = 1024, ns = 32: 112 KiB, one wave).  False where not even one wave fits.
+static bool ns_verify_shape(uint32_t W, uint32_t S, uint32_t ns, bool* f29, uint32_t* wave_words, uint32_t* wpb) {
+    *f29 = ns == 29 && S % 64 == 0 && S >= 64;
+    *wave_words = (W + 1u) * kNodeWords + (*f29 ? 0u : 64u * 16u * node_blocks(ns));
+    const size_t wave_bytes = (size_t)*wave_words * 4u;
+    uint32_t best = 0;
+    *wpb = 1;
+    for (uint32_t b = 1; b <= 4; ++b) {
+        if (b * wave_bytes > kLdsCap) break;
+        const uint32_t waves = (uint32_t)(kLdsCap / (b * wave_bytes)) * b;  // per CU
+        if (waves >= best) best = waves, *wpb = b;
+    }
+    return best != 0;
+}
+
 hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
                                 uint64_t shares_total, const uint8_t* d_roots, uint32_t W, uint32_t S, uint32_t ns,
                                 uint32_t k, uint32_t ignore_max, const NsQuery* d_queries, uint32_t n, uint32_t* d_status,
                                 hipStream_t st) {
     if (n == 0) return hipSuccess;
     if (!nmt_ns_verify_supported(W, ns)) return hipErrorInvalidValue;
-    const bool f29 = ns == 29 && S % 64 == 0 && S >= 64;
-    const uint32_t wave_words = (W + 1u) * kNodeWords + (f29 ? 0u : 64u * 16u * node_blocks(ns));
+    bool f29;
+    uint32_t wave_words, wpb;
+    if (!ns_verify_shape(W, S, ns, &f29, &wave_words, &wpb)) return hipErrorInvalidValue;
     const size_t wave_bytes = (size_t)wave_words * 4u;
-    uint32_t wpb = 1, best = 0;
-    for (uint32_t b = 1; b <= 4; ++b) {
-        if (b * wave_bytes > kLdsCap) break;
-        const uint32_t waves = (uint32_t)(kLdsCap / (b * wave_bytes)) * b;  // per CU
-        if (waves >= best) best = waves, wpb = b;
-    }
-    if (best == 0) return hipErrorInvalidValue;
     const uint32_t record_bytes = 16u + (2u * proof_levels(W) + 1u) * (2u * ns + 32u);
     const dim3 grid((n + wpb - 1) / wpb);
     if (f29)
@@ -1154,6 +1274,28 @@ hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offs
     else
         hipLaunchKernelGGL(nmt_ns_verify_kernel<0>, grid, dim3(64 * wpb), wpb * wave_bytes, st, d_records, d_offsets, d_shares,
                            shares_total, d_roots, W, S, ns, k, ignore_max, d_queries, n, record_bytes, wave_words, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmt_range_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                                   uint64_t shares_total, const uint8_t* d_roots, const uint8_t* d_root_records,
+                                   const uint8_t* d_data_roots, uint32_t W, uint32_t S, uint32_t ns, uint32_t k,
+                                   uint32_t ignore_max, const RangeQuery* d_queries, uint32_t n, uint32_t* d_status,
+                                   hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (!nmt_ns_verify_supported(W, ns)) return hipErrorInvalidValue;
+    bool f29;
+    uint32_t wave_words, wpb;
+    if (!ns_verify_shape(W, S, ns, &f29, &wave_words, &wpb)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)wpb * wave_words * 4u;
+    const uint32_t record_bytes = 16u + (2u * proof_levels(W) + 1u) * (2u * ns + 32u);
+    const dim3 grid((n + wpb - 1) / wpb), block(64 * wpb);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, d_records, d_offsets, d_shares, shares_total, d_roots, d_root_records,
+                           d_data_roots, W, S, ns, k, ignore_max, d_queries, n, record_bytes, wave_words, d_status);
+    };
+    if (d_root_records) f29 ? go(nmt_range_verify_kernel<29, true>) : go(nmt_range_verify_kernel<0, true>);
+    else f29 ? go(nmt_range_verify_kernel<29, false>) : go(nmt_range_verify_kernel<0, false>);
     return hipGetLastError();
 }
 

@@ -13,6 +13,10 @@
 //   ns_scan_kernel   : one workgroup turns the n counts into offsets[n + 1]
 //   ns_gather_kernel : one lane per (query, slot) of the 2L + 1 node slots
 //   ns_shares_kernel : one wave per query copies its shares, 16 bytes per lane
+// Range proofs (rsm_kernels.hpp "range proofs": the caller names [start, end) itself, of
+// either tree's store) put range_header_kernel in ns_locate_kernel's place and share the
+// other three: scan, gather and shares take a query as `qwords` words whose first three
+// are square, axis, index (NsQuery: 11, RangeQuery: 5).
 // Queries are validated on the host: no kernel sees a coordinate out of range.  start
 // and end are at most W by construction, so every node and share address is in range
 // whatever the store's namespaces are.
@@ -115,8 +119,25 @@ __global__ __launch_bounds__(256) void ns_locate_kernel(const uint32_t* __restri
     counts[q] = cnt;
 }
 
+// A range query's header, kind kNsInclusion over the caller's [start, end) (validated on
+// the host: start < end <= W), and its share count; nothing of the store is read.
+__global__ __launch_bounds__(256) void range_header_kernel(uint32_t W, uint32_t ns, const RangeQuery* __restrict__ queries,
+                                                           uint32_t n, uint8_t* __restrict__ records,
+                                                           uint32_t* __restrict__ counts) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= n) return;
+    const RangeQuery qu = queries[q];
+    uint32_t nl;
+    uint8_t* rec = records + (uint64_t)q * record_bytes(W, ns);
+    put_u32(rec, kNsInclusion);
+    put_u32(rec + 4, qu.start);
+    put_u32(rec + 8, qu.end);
+    put_u32(rec + 12, ns_range_nodes(W, qu.start, qu.end, &nl));
+    counts[q] = qu.end - qu.start;
+}
+
 // offs[0 .. n) hold counts; on return offs[i] = the sum of the counts before i, offs[n]
-// the total (below 2^32: n <= 2^20 queries of at most W <= 1024 shares).
+// the total (below 2^32: n <= 2^20 queries of at most W <= 2048 shares).
 __global__ __launch_bounds__(1024) void ns_scan_kernel(uint32_t* __restrict__ offs, uint32_t n) {
     __shared__ uint32_t wsum[16];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -148,8 +169,8 @@ __global__ __launch_bounds__(1024) void ns_scan_kernel(uint32_t* __restrict__ of
 
 __global__ __launch_bounds__(256) void ns_gather_kernel(const uint32_t* __restrict__ store, uint32_t W,
                                                         uint32_t squares, uint32_t ns,
-                                                        const NsQuery* __restrict__ queries, uint32_t n,
-                                                        uint8_t* records) {
+                                                        const uint32_t* __restrict__ queries, uint32_t qwords,
+                                                        uint32_t n, uint8_t* records) {
     const uint32_t L = proof_levels(W), slots = 2 * L + 1;
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (t >= (uint64_t)n * slots) return;
@@ -187,12 +208,13 @@ __global__ __launch_bounds__(256) void ns_gather_kernel(const uint32_t* __restri
         for (uint32_t i = 0; i < node_len; ++i) out[i] = 0;
         return;
     }
-    const NsQuery qu = queries[q];
-    store_node_bytes(store, W, squares, ns, qu.square, qu.axis, qu.index, lvl, j, out);
+    const uint32_t* qu = queries + (uint64_t)q * qwords;  // square, axis, index
+    store_node_bytes(store, W, squares, ns, qu[0], qu[1], qu[2], lvl, j, out);
 }
 
 __global__ __launch_bounds__(256) void ns_shares_kernel(const uint8_t* __restrict__ eds, uint32_t W, uint32_t S,
-                                                        uint32_t ns, const NsQuery* __restrict__ queries, uint32_t n,
+                                                        uint32_t ns, const uint32_t* __restrict__ queries,
+                                                        uint32_t qwords, uint32_t n,
                                                         const uint8_t* __restrict__ records,
                                                         const uint32_t* __restrict__ offs, uint8_t* __restrict__ shares,
                                                         uint64_t shares_cap) {
@@ -202,17 +224,32 @@ __global__ __launch_bounds__(256) void ns_shares_kernel(const uint8_t* __restric
     if (o1 == o0 || (uint64_t)o1 > shares_cap) return;  // nothing to copy, or it does not fit
     const uint32_t start = get_u32(records + (uint64_t)q * record_bytes(W, ns) + 4);
     const uint32_t qw = S / 16u, words = (o1 - o0) * qw;  // 16-byte words per share, of the query
-    const NsQuery qu = queries[q];
-    const uint8_t* sq = eds + (uint64_t)qu.square * W * W * S;
+    const uint32_t* qu = queries + (uint64_t)q * qwords;
+    const uint32_t square = qu[0], axis = qu[1], index = qu[2];
+    const uint8_t* sq = eds + (uint64_t)square * W * W * S;
     nq4u* dst = reinterpret_cast<nq4u*>(shares + (uint64_t)o0 * S);
     for (uint32_t w = lane; w < words; w += 64u) {
         const uint32_t p = start + w / qw, c = w % qw;
-        const uint64_t cell = qu.axis == 0 ? (uint64_t)qu.index * W + p : (uint64_t)p * W + qu.index;
+        const uint64_t cell = axis == 0 ? (uint64_t)index * W + p : (uint64_t)p * W + index;
         dst[w] = reinterpret_cast<const nq4u*>(sq + cell * S)[c];
     }
 }
 
 }  // namespace
+
+// scan, gather and shares behind either header kernel
+static hipError_t launch_scan_gather(const uint32_t* d_store, const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t squares,
+                                     uint32_t ns, const uint32_t* d_queries, uint32_t qwords, uint32_t n, uint8_t* d_records,
+                                     uint32_t* d_offsets, uint8_t* d_shares, uint64_t shares_cap, hipStream_t st) {
+    hipLaunchKernelGGL(ns_scan_kernel, dim3(1), dim3(1024), 0, st, d_offsets, n);
+    const uint64_t lanes = (uint64_t)n * (2 * proof_levels(W) + 1);
+    hipLaunchKernelGGL(ns_gather_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, d_store, W, squares,
+                       ns, d_queries, qwords, n, d_records);
+    if (d_shares)
+        hipLaunchKernelGGL(ns_shares_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d_eds, W, S, ns, d_queries, qwords, n,
+                           d_records, d_offsets, d_shares, shares_cap);
+    return hipGetLastError();
+}
 
 hipError_t launch_ns_proofs(const uint32_t* d_store, const uint32_t* d_status, const uint8_t* d_eds, uint32_t W,
                             uint32_t S, uint32_t squares, uint32_t ns, const NsQuery* d_queries, uint32_t n,
@@ -221,14 +258,18 @@ hipError_t launch_ns_proofs(const uint32_t* d_store, const uint32_t* d_status, c
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(ns_locate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_store, d_status, W, squares, ns,
                        d_queries, n, d_records, d_offsets);
-    hipLaunchKernelGGL(ns_scan_kernel, dim3(1), dim3(1024), 0, st, d_offsets, n);
-    const uint64_t lanes = (uint64_t)n * (2 * proof_levels(W) + 1);
-    hipLaunchKernelGGL(ns_gather_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, d_store, W, squares,
-                       ns, d_queries, n, d_records);
-    if (d_shares)
-        hipLaunchKernelGGL(ns_shares_kernel, dim3((n + 3) / 4), dim3(256), 0, st, d_eds, W, S, ns, d_queries, n,
-                           d_records, d_offsets, d_shares, shares_cap);
-    return hipGetLastError();
+    return launch_scan_gather(d_store, d_eds, W, S, squares, ns, reinterpret_cast<const uint32_t*>(d_queries),
+                              sizeof(NsQuery) / 4, n, d_records, d_offsets, d_shares, shares_cap, st);
+}
+
+hipError_t launch_range_proofs(const uint32_t* d_store, const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t squares,
+                               uint32_t ns, const RangeQuery* d_queries, uint32_t n, uint8_t* d_records,
+                               uint32_t* d_offsets, uint8_t* d_shares, uint64_t shares_cap, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_header_kernel, dim3((n + 255) / 256), dim3(256), 0, st, W, ns, d_queries, n, d_records,
+                       d_offsets);
+    return launch_scan_gather(d_store, d_eds, W, S, squares, ns, reinterpret_cast<const uint32_t*>(d_queries),
+                              sizeof(RangeQuery) / 4, n, d_records, d_offsets, d_shares, shares_cap, st);
 }
 
 }  // namespace rsm

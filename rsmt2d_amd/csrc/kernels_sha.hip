@@ -17,7 +17,8 @@
 // Also tree_nodes_kernel (every node kept: the proofs' node store),
 // proof_verify_kernel (one lane per sampled share: leaf hash, fold of its proof, compare
 // with the committed root) and proof_verify_data_root_kernel (the same lane, folding on
-// through the root's proof under the square's data root).
+// through the root's proof under the square's data root) and range_verify_kernel (one wave
+// per range proof: the leaves of the range, the fold in the wave's LDS; any width up to 2048).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -405,7 +406,157 @@ __global__ __launch_bounds__(256) void proof_verify_data_root_kernel(
     status[t] = data_root_matches(g, rrec, n2, mask2, data_roots + (uint64_t)sm.square * 32u) ? kProofOk : kProofRoot;
 }
 
+// Range proof verification (rsm_kernels.hpp "range proofs"), DefaultTree: one WAVE per
+// query, the picture of kernels_nmt.hip's namespace verifier with 8-word digests.  The
+// wave's LDS holds one tree level in place, node p of a level at entry p (W entries and a
+// spare one); no workgroup barrier: the waves of a workgroup share nothing.
+//   header : the two offsets first (kProofMalformed: nothing else of the query is read),
+//            then the record's header against the QUERY's [start, end) (host-validated:
+//            start < end <= W) and the node count it dictates, then (CHAINED) the root
+//            record's against (2W, axis W + index)
+//   leaves : lane j hashes shares j, j + 64, .. into entries start + j, ..
+//   fold   : level l grafts the left proof node at entry a - 1 when a is odd and the right
+//            one at last + 1 when last is even and below the level's last node; lane j joins
+//            entries a + 2j, a + 2j + 1 into entry a / 2 + j (both reads at or past the
+//            write; a pass's reads precede its writes), an unpaired last entry is carried up
+// Every lane hashes in every pass: past a pass's last leaf (node) a lane repeats one of the
+// pass and stores it to the spare entry (a wave with few lanes active runs its SHA rounds
+// slower per compression, see above).  Every address comes from (W, start, end) and the
+// offsets; nothing of a record past its derived nodes is read.
+constexpr size_t kRangeLdsCap = 160 * 1024 - 256;  // per workgroup
+
+template <bool CHAINED>
+__global__ __launch_bounds__(256) void range_verify_kernel(
+    const uint8_t* __restrict__ records, const uint32_t* __restrict__ offsets, const uint8_t* __restrict__ shares,
+    uint64_t shares_total, const uint8_t* __restrict__ roots, const uint8_t* __restrict__ root_records,
+    const uint8_t* __restrict__ data_roots, uint32_t W, uint32_t S, const RangeQuery* __restrict__ queries, uint32_t n,
+    uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t lds[];  // per wave: W digests and a spare one
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * (blockDim.x >> 6) + wv;
+    if (q >= n) return;
+    uint32_t* const row = lds + (size_t)wv * (W + 1u) * 8u;
+    uint32_t* const spare = row + (size_t)W * 8u;
+    auto done = [&](uint32_t st) {
+        if (lane == 0) status[q] = st;
+    };
+    const uint32_t o0 = __builtin_amdgcn_readfirstlane(offsets[q]), o1 = __builtin_amdgcn_readfirstlane(offsets[q + 1]);
+    if (o0 > o1 || o1 > shares_total) return done(kProofMalformed);
+    const RangeQuery qu = queries[q];
+    const uint32_t start = __builtin_amdgcn_readfirstlane(qu.start), end = __builtin_amdgcn_readfirstlane(qu.end);
+    const uint32_t L = proof_levels(W);
+    const uint8_t* rec = records + (uint64_t)q * (16u + (2u * L + 1u) * 32u);
+    if (o1 - o0 != end - start || ld_u32(rec) != kNsInclusion || ld_u32(rec + 4) != start || ld_u32(rec + 8) != end)
+        return done(kProofMalformed);
+    uint32_t n_left = 0;
+    if (ld_u32(rec + 12) != ns_range_nodes(W, start, end, &n_left)) return done(kProofMalformed);
+    const uint8_t* rrec = nullptr;
+    uint32_t n2 = 0, mask2 = 0;
+    if constexpr (CHAINED) {
+        rrec = root_records + (uint64_t)q * (8u + proof_levels(2u * W) * 32u);
+        n2 = proof_shape(2u * W, qu.axis * W + qu.index, &mask2);
+        if (ld_u32(rrec) != n2 || ld_u32(rrec + 4) != mask2) return done(kProofMalformed);
+    }
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    auto put = [](uint32_t* p, const uint32_t (&d)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) p[i] = d[i];
+    };
+    auto get = [](const uint32_t* p, uint32_t (&d)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = p[i];
+    };
+    auto graft = [&](uint32_t entry, uint32_t node) {  // proof node `node` of the record into a level's entry
+        if (lane == 0) {
+            uint32_t d[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d[i] = __builtin_bswap32(ld_u32(rec + 16u + node * 32u + 4 * i));
+            put(row + (size_t)entry * 8u, d);
+        }
+    };
+    for (uint32_t i0 = 0, n_shares = end - start; i0 < n_shares; i0 += 64u) {
+        const uint32_t rem = n_shares - i0;
+        const bool own = lane < rem;
+        const uint32_t i = i0 + (own ? lane : lane % rem);
+        uint32_t h[8];
+        share_leaf_hash(shares + ((uint64_t)o0 + i) * S, S, h);
+        put(own ? row + (size_t)(start + i) * 8u : spare, h);
+    }
+    uint32_t a = start, last = end - 1u, li = n_left, ri = n_left;  // next left node: li - 1; next right: ri
+    for (uint32_t l = 0; l < L; ++l) {
+        if (a & 1u) graft(--a, --li);
+        if (!(last & 1u) && last + 1u < proof_level_count(W, l)) graft(++last, ri++);
+        wave_sync();  // the leaves / the level below and the grafts are written
+        const uint32_t have = last - a + 1u, np = have / 2u, up = np + (have & 1u);  // a is even
+        for (uint32_t v0 = 0; v0 < up; v0 += 64u) {
+            const uint32_t rem = up - v0;
+            const bool own = lane < rem;
+            const uint32_t j = v0 + (own ? lane : lane % rem);
+            uint32_t x[8], o[8];
+            get(row + (size_t)(a + 2u * j) * 8u, x);
+            if (j < np) {
+                uint32_t y[8];
+                get(row + (size_t)(a + 2u * j + 1u) * 8u, y);
+                node_hash(x, y, o);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) o[i] = x[i];  // carried up unchanged
+            }
+            wave_sync();  // every lane's reads of this pass before any write (a / 2 + j <= a + 2 j)
+            put(own ? row + (size_t)(a / 2u + j) * 8u : spare, o);
+        }
+        a >>= 1;
+        last >>= 1;
+    }
+    wave_sync();
+    uint32_t h[8];
+    get(row, h);
+    if constexpr (CHAINED) {
+        uint32_t B[kRootWords], g[8];  // the candidate root: the digest itself
+#pragma unroll
+        for (int i = 0; i < kRootWords; ++i) B[i] = i < 8 ? h[i] : 0u;
+        root_leaf_hash(B, 32u, g);
+        done(data_root_matches(g, rrec, n2, mask2, data_roots + (uint64_t)qu.square * 32u) ? kProofOk : kProofRoot);
+    } else {
+        const uint8_t* rt = roots + (((uint64_t)qu.square * 2u + qu.axis) * W + qu.index) * 32u;
+        done(digest_differs(h, rt) ? kProofRoot : kProofOk);
+    }
+}
+
 }  // namespace
+
+bool range_verify_supported(uint32_t W, uint32_t ns) {
+    return ns == 0 ? W >= 1 && W <= 2 * kMaxLevel1 : nmt_ns_verify_supported(W, ns);
+}
+
+// One wave per query, up to four waves per workgroup: the count that lets most waves share
+// a CU's LDS, as launch_nmt_ns_verify (W = 2048: 64 KiB a wave, two per CU).
+hipError_t launch_range_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                               uint64_t shares_total, const uint8_t* d_roots, const uint8_t* d_root_records,
+                               const uint8_t* d_data_roots, uint32_t W, uint32_t S, const RangeQuery* d_queries, uint32_t n,
+                               uint32_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (!range_verify_supported(W, 0)) return hipErrorInvalidValue;
+    const size_t wave_bytes = (size_t)(W + 1u) * 32u;
+    uint32_t wpb = 1, best = 0;
+    for (uint32_t b = 1; b <= 4; ++b) {
+        if (b * wave_bytes > kRangeLdsCap) break;
+        const uint32_t waves = (uint32_t)(kRangeLdsCap / (b * wave_bytes)) * b;  // per CU
+        if (waves >= best) best = waves, wpb = b;
+    }
+    const dim3 grid((n + wpb - 1) / wpb), block(64 * wpb);
+    if (d_root_records)
+        hipLaunchKernelGGL(range_verify_kernel<true>, grid, block, wpb * wave_bytes, st, d_records, d_offsets, d_shares,
+                           shares_total, d_roots, d_root_records, d_data_roots, W, S, d_queries, n, d_status);
+    else
+        hipLaunchKernelGGL(range_verify_kernel<false>, grid, block, wpb * wave_bytes, st, d_records, d_offsets, d_shares,
+                           shares_total, d_roots, d_root_records, d_data_roots, W, S, d_queries, n, d_status);
+    return hipGetLastError();
+}
 
 hipError_t launch_proof_verify(const uint8_t* d_shares, const uint8_t* d_records, const uint8_t* d_roots, uint32_t W,
                                uint32_t S, const ProofSample* d_samples, uint32_t n, uint32_t* d_status, hipStream_t st) {

@@ -822,6 +822,96 @@ uint32_t get_le32(const uint8_t* p) {
     return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
 }
 
+// Every level of the tree over the n level-0 nodes in lv[0] (NB bytes each) into lv[1 .. L];
+// `join` as prove_levels takes it (false: tree error).
+template <typename Join>
+bool build_levels(std::vector<std::vector<uint8_t>>& lv, uint32_t n, uint32_t NB, Join&& join) {
+    for (uint32_t l = 0, cnt = n; l + 1 < lv.size(); ++l) {
+        const uint32_t np = cnt / 2, up = (cnt + 1) / 2;
+        lv[l + 1].assign((size_t)up * NB, 0);
+        if (!join(lv[l].data(), np, lv[l + 1].data())) return false;
+        if (cnt & 1u) memcpy(&lv[l + 1][(size_t)np * NB], &lv[l][(size_t)(cnt - 1) * NB], NB);
+        cnt = up;
+    }
+    return true;
+}
+
+// Header (kind | start | end | n_nodes) and range-proof nodes of [start, end) out of the
+// levels lv of a tree of n leaves; the caller zeroed the record.
+void put_range_record(uint8_t* rec, uint32_t kind, const std::vector<std::vector<uint8_t>>& lv, uint32_t n, uint32_t NB,
+                      uint32_t start, uint32_t end) {
+    uint32_t n_left;
+    const std::vector<RangeNode> nodes = range_nodes(n, start, end, &n_left);
+    put_le32(rec, kind);
+    put_le32(rec + 4, start);
+    put_le32(rec + 8, end);
+    put_le32(rec + 12, (uint32_t)nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i) memcpy(rec + 16 + i * NB, &lv[nodes[i].level][(size_t)nodes[i].j * NB], NB);
+}
+
+// The fold of a range proof, level by level: cur holds the range's nodes a .. last of a
+// level (level 0: leaves start .. end - 1), the proof's left node goes in front when a is
+// odd, its right node behind when last is even and not the level's last node; an unpaired
+// last node is carried up.  join(l, out): the parent of the adjacent nodes l, l + NB
+// (false: unordered siblings).  Leaves the root in cur; false on a failed join.
+template <typename Join>
+bool fold_range(std::vector<uint8_t>& cur, uint32_t n_leaves, uint32_t NB, uint32_t start, uint32_t end, uint32_t n_left,
+                const uint8_t* record, Join&& join) {
+    uint32_t a = start, last = end - 1, li = n_left, ri = n_left;  // next left node: li - 1; next right: ri
+    std::vector<uint8_t> row, nxt;
+    for (uint32_t l = 0, L = proof_levels_of(n_leaves); l < L; ++l) {
+        const uint32_t cnt = (uint32_t)(((uint64_t)n_leaves + (1ull << l) - 1) >> l);
+        row.clear();
+        if (a & 1u) {
+            const uint8_t* nd = record + 16 + (size_t)(--li) * NB;
+            row.insert(row.end(), nd, nd + NB);
+            --a;
+        }
+        row.insert(row.end(), cur.begin(), cur.end());
+        if (!(last & 1u) && last + 1 < cnt) {
+            const uint8_t* nd = record + 16 + (size_t)(ri++) * NB;
+            row.insert(row.end(), nd, nd + NB);
+            ++last;
+        }
+        const uint32_t have = last - a + 1, np = have / 2;  // a is even; an odd count ends in the carried node
+        nxt.assign((size_t)(np + (have & 1u)) * NB, 0);
+        for (uint32_t j = 0; j < np; ++j)
+            if (!join(&row[(size_t)2 * j * NB], &nxt[(size_t)j * NB])) return false;
+        if (have & 1u) memcpy(&nxt[(size_t)np * NB], &row[(size_t)(have - 1) * NB], NB);
+        cur.swap(nxt);
+        a >>= 1;
+        last >>= 1;
+    }
+    return true;
+}
+
+// HashNode of the adjacent NMT nodes l, l + NB into out; false: unordered siblings
+bool nmt_join(const uint8_t* l, uint8_t* out, uint32_t nsz, bool ig) {
+    const uint32_t NB = 2 * nsz + 32;
+    if (!nmt_pair(l, l + NB, nsz, ig, out)) return false;
+    Sha256 s;
+    const uint8_t pre = 0x01;
+    s.update(&pre, 1);
+    s.update(l, 2 * (size_t)NB);
+    s.final(out + 2 * nsz);
+    return true;
+}
+
+// the wrapper's NMT leaf node of leaf p of vector `index`: ns || ns || H(0x00 || ns || share)
+void nmt_leaf_node(const rsm_nmt_params* p, uint32_t index, uint32_t pos, const uint8_t* share, uint32_t share_size,
+                   uint8_t* out) {
+    const uint32_t nsz = p->namespace_size, k = p->square_size;
+    if (index < k && pos < k) memcpy(out, share, nsz);  // quadrant 0
+    else memset(out, 0xFF, nsz);
+    memcpy(out + nsz, out, nsz);
+    Sha256 s;
+    const uint8_t pre = 0x00;
+    s.update(&pre, 1);
+    s.update(out, nsz);
+    s.update(share, share_size);
+    s.final(out + 2 * nsz);
+}
+
 }  // namespace
 
 extern "C" uint32_t rsm_ns_record_bytes(uint32_t width, const rsm_nmt_params* nmt) {
@@ -838,13 +928,8 @@ extern "C" int rsm_nmt_namespace_prove(const rsm_nmt_params* p, uint32_t index, 
     const bool ig = p->ignore_max_namespace != 0;
     std::vector<std::vector<uint8_t>> lv(L + 1);  // every level of the tree
     if (int rc = nmt_leaf_level(p, index, leaves, n_leaves, leaf_size, lv[0])) return rc;
-    for (uint32_t l = 0, cnt = n_leaves; l < L; ++l) {
-        const uint32_t np = cnt / 2, up = (cnt + 1) / 2;
-        lv[l + 1].assign((size_t)up * NB, 0);
-        if (!nmt_join_pairs(lv[l].data(), np, lv[l + 1].data(), nsz, ig)) return RSM_ETREE;
-        if (cnt & 1u) memcpy(&lv[l + 1][(size_t)np * NB], &lv[l][(size_t)(cnt - 1) * NB], NB);
-        cnt = up;
-    }
+    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) { return nmt_join_pairs(cur, np, out, nsz, ig); };
+    if (!build_levels(lv, n_leaves, NB, join)) return RSM_ETREE;
     const uint8_t* root = lv[L].data();
     if (root_out) memcpy(root_out, root, NB);
     memset(record_out, 0, rsm_ns_record_bytes(n_leaves, p));
@@ -858,14 +943,7 @@ extern "C" int rsm_nmt_namespace_prove(const rsm_nmt_params* p, uint32_t index, 
         end = start + 1;
         memcpy(record_out + 16 + (size_t)2 * L * NB, &lv[0][(size_t)start * NB], NB);
     }
-    uint32_t n_left;
-    const std::vector<RangeNode> nodes = range_nodes(n_leaves, start, end, &n_left);
-    put_le32(record_out, absent ? RSM_NS_ABSENCE : RSM_NS_INCLUSION);
-    put_le32(record_out + 4, start);
-    put_le32(record_out + 8, end);
-    put_le32(record_out + 12, (uint32_t)nodes.size());
-    for (size_t i = 0; i < nodes.size(); ++i)
-        memcpy(record_out + 16 + i * NB, &lv[nodes[i].level][(size_t)nodes[i].j * NB], NB);
+    put_range_record(record_out, absent ? RSM_NS_ABSENCE : RSM_NS_INCLUSION, lv, n_leaves, NB, start, end);
     return RSM_OK;
 }
 
@@ -876,7 +954,7 @@ extern "C" int rsm_nmt_namespace_verify(const rsm_nmt_params* p, uint32_t index,
     if (!p || !nid || !record || !root || !status || (n_shares && !shares) || p->namespace_size == 0 ||
         p->square_size == 0 || n_leaves == 0)
         return RSM_EINVAL;
-    const uint32_t nsz = p->namespace_size, k = p->square_size, NB = 2 * nsz + 32, L = proof_levels_of(n_leaves);
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32, L = proof_levels_of(n_leaves);
     const bool ig = p->ignore_max_namespace != 0;
     if (n_shares && share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
     const uint32_t kind = get_le32(record), start = get_le32(record + 4), end = get_le32(record + 8),
@@ -902,22 +980,12 @@ extern "C" int rsm_nmt_namespace_verify(const rsm_nmt_params* p, uint32_t index,
     const std::vector<RangeNode> shape = range_nodes(n_leaves, start, end, &n_left);
     if (n_nodes != shape.size()) return done(RSM_PROOF_MALFORMED);
     // 2. the leaves carry nid / the absence leaf is one leaf above nid
-    std::vector<uint8_t> cur((size_t)(end - start) * NB), ns(nsz);
+    std::vector<uint8_t> cur((size_t)(end - start) * NB);
     if (kind == RSM_NS_INCLUSION) {
         for (uint32_t i = 0; i < n_shares; ++i) {
-            const uint8_t* sh = shares + (size_t)i * share_size;
-            if (index < k && start + i < k) memcpy(ns.data(), sh, nsz);  // quadrant 0
-            else memset(ns.data(), 0xFF, nsz);
-            if (memcmp(ns.data(), nid, nsz) != 0) return done(RSM_PROOF_NAMESPACE);
             uint8_t* o = &cur[(size_t)i * NB];
-            memcpy(o, ns.data(), nsz);
-            memcpy(o + nsz, ns.data(), nsz);
-            Sha256 s;
-            const uint8_t pre = 0x00;
-            s.update(&pre, 1);
-            s.update(ns.data(), nsz);
-            s.update(sh, share_size);
-            s.final(o + 2 * nsz);
+            nmt_leaf_node(p, index, start + i, shares + (size_t)i * share_size, share_size, o);
+            if (memcmp(o, nid, nsz) != 0) return done(RSM_PROOF_NAMESPACE);
         }
     } else {
         const uint8_t* leaf = record + 16 + (size_t)2 * L * NB;
@@ -929,41 +997,117 @@ extern "C" int rsm_nmt_namespace_verify(const rsm_nmt_params* p, uint32_t index,
         const uint8_t* nd = record + 16 + (size_t)i * NB;
         if (i < n_left ? memcmp(nd + nsz, nid, nsz) >= 0 : memcmp(nd, nid, nsz) <= 0) return done(RSM_PROOF_INCOMPLETE);
     }
-    // 4, 5. the fold, level by level: the range's nodes a .. last of a level, the proof's
-    // left node in front when a is odd, its right node behind when last is even and not
-    // the level's last node; an unpaired last node is carried up
-    uint32_t a = start, last = end - 1, li = n_left, ri = n_left;  // next left node: li - 1; next right: ri
-    std::vector<uint8_t> row, nxt;
-    for (uint32_t l = 0; l < L; ++l) {
-        const uint32_t cnt = (uint32_t)(((uint64_t)n_leaves + (1ull << l) - 1) >> l);
-        row.clear();
-        if (a & 1u) {
-            const uint8_t* nd = record + 16 + (size_t)(--li) * NB;
-            row.insert(row.end(), nd, nd + NB);
-            --a;
-        }
-        row.insert(row.end(), cur.begin(), cur.end());
-        if (!(last & 1u) && last + 1 < cnt) {
-            const uint8_t* nd = record + 16 + (size_t)(ri++) * NB;
-            row.insert(row.end(), nd, nd + NB);
-            ++last;
-        }
-        const uint32_t have = last - a + 1, np = have / 2;  // a is even; an odd count ends in the carried node
-        nxt.assign((size_t)(np + (have & 1u)) * NB, 0);
-        for (uint32_t j = 0; j < np; ++j) {
-            const uint8_t* lft = &row[(size_t)2 * j * NB];
-            uint8_t* o = &nxt[(size_t)j * NB];
-            if (!nmt_pair(lft, lft + NB, nsz, ig, o)) return done(RSM_PROOF_ORDER);
-            Sha256 s;
-            const uint8_t pre = 0x01;
-            s.update(&pre, 1);
-            s.update(lft, 2 * (size_t)NB);
-            s.final(o + 2 * nsz);
-        }
-        if (have & 1u) memcpy(&nxt[(size_t)np * NB], &row[(size_t)(have - 1) * NB], NB);
-        cur.swap(nxt);
-        a >>= 1;
-        last >>= 1;
-    }
+    // 4, 5. the fold
+    if (!fold_range(cur, n_leaves, NB, start, end, n_left, record,
+                    [&](const uint8_t* l, uint8_t* o) { return nmt_join(l, o, nsz, ig); }))
+        return done(RSM_PROOF_ORDER);
     return done(memcmp(cur.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT);
+}
+
+// ---- range proofs (include/rsmt2d_hip.h "range proofs") ----
+// Host restatements of rsm_range_proofs_dev and the range verify kernels: the namespace
+// record of kind INCLUSION over the caller's [start, end), of either tree; the verifiers
+// bind the record to the caller's start and end and fold as the namespace verifier does.
+extern "C" int rsm_default_tree_range_prove(const uint8_t* const* leaves, uint32_t n_leaves, uint32_t leaf_size,
+                                            uint32_t start, uint32_t end, uint8_t* record_out, uint8_t* root_out) {
+    if (!leaves || !record_out || n_leaves == 0 || !(start < end && end <= n_leaves)) return RSM_EINVAL;
+    for (uint32_t i = 0; i < n_leaves; ++i)
+        if (!leaves[i]) return RSM_ETREE;
+    const uint32_t L = proof_levels_of(n_leaves);
+    std::vector<std::vector<uint8_t>> lv(L + 1);
+    lv[0].resize((size_t)n_leaves * 32);
+    Digest dg[kHashBatch];
+    for (uint32_t i = 0; i < n_leaves; i += kHashBatch) {
+        const int c = (int)std::min<uint32_t>(kHashBatch, n_leaves - i);
+        hash_prefixed(0x00, leaves + i, c, leaf_size, dg);
+        for (int q = 0; q < c; ++q) memcpy(&lv[0][(size_t)(i + q) * 32], dg[q].b, 32);
+    }
+    build_levels(lv, n_leaves, 32, digest_join_pairs);
+    if (root_out) memcpy(root_out, lv[L].data(), 32);
+    memset(record_out, 0, 16 + (size_t)(2 * L + 1) * 32);
+    put_range_record(record_out, RSM_NS_INCLUSION, lv, n_leaves, 32, start, end);
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_tree_range_prove(const rsm_nmt_params* p, uint32_t index, const uint8_t* const* leaves,
+                                        uint32_t n_leaves, uint32_t leaf_size, uint32_t start, uint32_t end,
+                                        uint8_t* record_out, uint8_t* root_out) {
+    if (!p || !leaves || !record_out || p->namespace_size == 0 || p->square_size == 0 || n_leaves == 0 ||
+        !(start < end && end <= n_leaves))
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32, L = proof_levels_of(n_leaves);
+    const bool ig = p->ignore_max_namespace != 0;
+    std::vector<std::vector<uint8_t>> lv(L + 1);
+    if (int rc = nmt_leaf_level(p, index, leaves, n_leaves, leaf_size, lv[0])) return rc;
+    auto join = [&](const uint8_t* cur, uint32_t np, uint8_t* out) { return nmt_join_pairs(cur, np, out, nsz, ig); };
+    if (!build_levels(lv, n_leaves, NB, join)) return RSM_ETREE;
+    if (root_out) memcpy(root_out, lv[L].data(), NB);
+    memset(record_out, 0, 16 + (size_t)(2 * L + 1) * NB);
+    put_range_record(record_out, RSM_NS_INCLUSION, lv, n_leaves, NB, start, end);
+    return RSM_OK;
+}
+
+namespace {
+
+// rule 1 of the range verifiers: the record against the caller's question
+bool range_header_ok(const uint8_t* record, uint32_t n_leaves, uint32_t start, uint32_t end, uint32_t n_shares,
+                     uint32_t* n_left) {
+    if (n_shares != end - start || get_le32(record) != RSM_NS_INCLUSION || get_le32(record + 4) != start ||
+        get_le32(record + 8) != end)
+        return false;
+    return get_le32(record + 12) == range_nodes(n_leaves, start, end, n_left).size();
+}
+
+}  // namespace
+
+extern "C" int rsm_default_tree_range_verify(uint32_t start, uint32_t end, const uint8_t* shares, uint32_t n_shares,
+                                             uint32_t share_size, uint32_t n_leaves, const uint8_t* record,
+                                             const uint8_t* root, uint32_t* status) {
+    if (!record || !root || !status || (n_shares && share_size && !shares) || n_leaves == 0 || !(start < end && end <= n_leaves))
+        return RSM_EINVAL;
+    uint32_t n_left = 0;
+    if (!range_header_ok(record, n_leaves, start, end, n_shares, &n_left)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    std::vector<uint8_t> cur((size_t)n_shares * 32);
+    for (uint32_t i = 0; i < n_shares; ++i) {
+        const Digest d = leaf_hash(shares + (size_t)i * share_size, share_size);
+        memcpy(&cur[(size_t)i * 32], d.b, 32);
+    }
+    fold_range(cur, n_leaves, 32, start, end, n_left, record, [](const uint8_t* l, uint8_t* o) {
+        Digest a, b;
+        memcpy(a.b, l, 32);
+        memcpy(b.b, l + 32, 32);
+        memcpy(o, node_hash(a, b).b, 32);
+        return true;
+    });
+    *status = memcmp(cur.data(), root, 32) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
+}
+
+extern "C" int rsm_nmt_tree_range_verify(const rsm_nmt_params* p, uint32_t index, uint32_t start, uint32_t end,
+                                         const uint8_t* shares, uint32_t n_shares, uint32_t share_size, uint32_t n_leaves,
+                                         const uint8_t* record, const uint8_t* root, uint32_t* status) {
+    if (!p || !record || !root || !status || (n_shares && !shares) || p->namespace_size == 0 || p->square_size == 0 ||
+        n_leaves == 0 || !(start < end && end <= n_leaves))
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    if (share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
+    uint32_t n_left = 0;
+    if (!range_header_ok(record, n_leaves, start, end, n_shares, &n_left)) {
+        *status = RSM_PROOF_MALFORMED;
+        return RSM_OK;
+    }
+    std::vector<uint8_t> cur((size_t)n_shares * NB);
+    for (uint32_t i = 0; i < n_shares; ++i)
+        nmt_leaf_node(p, index, start + i, shares + (size_t)i * share_size, share_size, &cur[(size_t)i * NB]);
+    if (!fold_range(cur, n_leaves, NB, start, end, n_left, record,
+                    [&](const uint8_t* l, uint8_t* o) { return nmt_join(l, o, nsz, ig); })) {
+        *status = RSM_PROOF_ORDER;
+        return RSM_OK;
+    }
+    *status = memcmp(cur.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
+    return RSM_OK;
 }

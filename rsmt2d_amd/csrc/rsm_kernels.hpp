@@ -284,6 +284,40 @@ hipError_t launch_nmt_ns_verify(const uint8_t* d_records, const uint32_t* d_offs
                                 uint64_t shares_total, const uint8_t* d_roots, uint32_t W, uint32_t S, uint32_t ns,
                                 uint32_t k, uint32_t ignore_max, const NsQuery* d_queries, uint32_t n, uint32_t* d_status,
                                 hipStream_t st);
+// ---- range proofs (DESIGN.md §4 "Range proofs") ---------------------------------------
+// A query: leaves [start, end) of row / column `index` of square `square` (the C ABI's
+// rsm_range_query).  Its record is the namespace record of kind kNsInclusion over the
+// caller's range, out of either tree's store (ns = 0: DefaultTree, 32-byte nodes).
+struct RangeQuery {
+    uint32_t square, axis, index, start, end;
+};
+// launch_ns_proofs with a header kernel in locate's place (kernels_nsproof.hip): one lane
+// per query writes kind | start | end | n_nodes and the share count end - start; scan,
+// gather and shares are the namespace proofs' kernels.  Queries are validated on the host
+// (start < end <= W).
+hipError_t launch_range_proofs(const uint32_t* d_store, const uint8_t* d_eds, uint32_t W, uint32_t S, uint32_t squares,
+                               uint32_t ns, const RangeQuery* d_queries, uint32_t n, uint8_t* d_records,
+                               uint32_t* d_offsets, uint8_t* d_shares, uint64_t shares_cap, hipStream_t st);
+// Range proof verification (NMT: kernels_nmt.hip, DefaultTree: kernels_sha.hip): one wave
+// per query, as launch_nmt_ns_verify.  Query i: are shares [d_offsets[i], d_offsets[i + 1])
+// of d_shares leaves [start, end) of vector (square, axis, index), by record i, under root
+// (square, axis, index) of d_roots?  kProofMalformed (the offsets, then the record's header
+// against the QUERY's start and end and the node count they dictate), kProofOrder (NMT),
+// kProofRoot, kProofOk.  d_root_records non-null: the chained form -- d_roots is not read;
+// root record i ([n][8 + L2 * 32]) is checked against (2W, axis W + index) with the other
+// headers, the fold's root is hashed as that leaf of the data-root tree, folded on and
+// compared with d_data_roots[square].  ns = 0 is not taken by the NMT launch; W <= 1024
+// (NMT), 2048 (DefaultTree): a wave's LDS holds W nodes.
+bool range_verify_supported(uint32_t W, uint32_t ns);  // ns = 0: DefaultTree
+hipError_t launch_nmt_range_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                                   uint64_t shares_total, const uint8_t* d_roots, const uint8_t* d_root_records,
+                                   const uint8_t* d_data_roots, uint32_t W, uint32_t S, uint32_t ns, uint32_t k,
+                                   uint32_t ignore_max, const RangeQuery* d_queries, uint32_t n, uint32_t* d_status,
+                                   hipStream_t st);
+hipError_t launch_range_verify(const uint8_t* d_records, const uint32_t* d_offsets, const uint8_t* d_shares,
+                               uint64_t shares_total, const uint8_t* d_roots, const uint8_t* d_root_records,
+                               const uint8_t* d_data_roots, uint32_t W, uint32_t S, const RangeQuery* d_queries, uint32_t n,
+                               uint32_t* d_status, hipStream_t st);
 // ---- data root (DESIGN.md §4 "Data root"; kernels_dataroot.hip) ----------------------
 // The tree over the N = 2W roots of a square (leaf t: the root bytes of tree t, rows then
 // columns, root_len = 32 .. 96 bytes each), in the level picture above with 32-byte

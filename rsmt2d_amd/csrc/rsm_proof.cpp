@@ -8,7 +8,9 @@
 // rsm_ns_proofs_verify_dev over nmt_ns_verify_kernel (kernels_nmt.hip); the data root:
 // rsm_data_roots_dev and rsm_root_proofs_dev over kernels_dataroot.hip, and
 // rsm_proofs_verify_data_root_dev over the chained verify kernels, and rsm_eds_data_root
-// (the roots on the device as rsm_eds_roots computes them, then the data root there).
+// (the roots on the device as rsm_eds_roots computes them, then the data root there); range
+// proofs: rsm_range_proofs_dev over kernels_nsproof.hip, rsm_range_proofs_verify_dev and its
+// chained form over the range verify kernels, rsm_eds_range_proofs, rsm_share_range_queries.
 // Formats: include/rsmt2d_hip.h.
 #include "eds_internal.hpp"
 
@@ -25,6 +27,9 @@ static_assert(sizeof(rsm_root_ref) == sizeof(RootRef) && sizeof(rsm_root_ref) ==
 static_assert(sizeof(NsQuery) == 44&& kNsEmpty == RSM_NS_EMPTY && kNsInclusion == RSM_NS_INCLUSION &&
                   kNsAbsence == RSM_NS_ABSENCE && kNsTree == RSM_NS_TREE,
               "the kernels' namespace proof kinds are the C ABI's");
+
+static_assert(sizeof(rsm_range_query) == sizeof(RangeQuery) && sizeof(rsm_range_query) == 20,
+              "rsm_range_query is the kernels' range query");
 
 static_assert(kProofOk == RSM_PROOF_OK && kProofMalformed == RSM_PROOF_MALFORMED && kProofOrder == RSM_PROOF_ORDER &&
                   kProofRoot == RSM_PROOF_ROOT && kProofNamespace == RSM_PROOF_NAMESPACE &&
@@ -91,6 +96,56 @@ int pack_ns_queries(const char* fn, const rsm_ns_query* queries, const uint8_t* 
         for (uint32_t b = 0; b < ns; ++b) q.nid[b >> 2] |= (uint32_t)nids[(size_t)i * ns + b] << (24u - 8u * (b & 3u));
     }
     return RSM_OK;
+}
+
+int check_range_queries(const char* fn, const rsm_range_query* q, uint32_t n, uint32_t count, uint32_t width) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (q[i].square >= count || q[i].axis > 1 || q[i].index >= width || !(q[i].start < q[i].end && q[i].end <= width))
+            return fail(RSM_EINVAL, "%s: query %u (square %u, axis %u, index %u, leaves [%u, %u)) is out of range", fn, i,
+                        q[i].square, q[i].axis, q[i].index, q[i].start, q[i].end);
+    return RSM_OK;
+}
+
+// The two range verification calls: their checks before any device use, in
+// rsm_ns_proofs_verify_dev's order (`operands`: the call's pointers are all there), then
+// the queries staged and the launch; d_roots or (chained) d_root_records / d_data_roots.
+int range_verify_call(const char* fn, rsm_ctx* ctx, bool operands, const void* d_records, const void* d_offsets,
+                      const void* d_shares, uint64_t shares_total, const void* d_roots, const void* d_root_records,
+                      const void* d_data_roots, uint32_t width, uint32_t share_size, uint32_t count,
+                      const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n, void* d_status, void* stream) {
+    if (!ctx || width == 0 || (n && count && (!operands || (shares_total && !d_shares))))
+        return fail(RSM_EINVAL, "%s: bad arguments", fn);
+    if (nmt && (nmt->namespace_size == 0 || nmt->namespace_size > 32 || nmt->square_size == 0))
+        return fail(RSM_EINVAL, "%s: namespace size %u (1..32) or square size 0", fn, nmt->namespace_size);
+    if (reinterpret_cast<uintptr_t>(d_shares) & 15u) return fail(RSM_EINVAL, "%s: d_shares must be 16-byte aligned", fn);
+    if ((reinterpret_cast<uintptr_t>(d_offsets) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return fail(RSM_EINVAL, "%s: d_offsets and d_status must be 4-byte aligned", fn);
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    if (!range_verify_supported(width, nmt ? nmt->namespace_size : 0u))
+        return fail(RSM_EUNSUPPORTED, "%s: width %u not supported (at most %u)", fn, width, nmt ? 1024u : 2048u);
+    if (nmt && share_size < nmt->namespace_size) return fail(RSM_ETREE, "data is too short to contain namespace ID");
+    if (n > (1u << 20)) return fail(RSM_EINVAL, "%s: at most %u queries per call", fn, 1u << 20);
+    if (n == 0 || count == 0) return RSM_OK;
+    if (int rc = check_range_queries(fn, queries, n, count, width)) return rc;
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const void* dq = nullptr;
+    if (int rc = stage_bytes(st, ss, queries, (size_t)n * sizeof(rsm_range_query), &dq)) return rc;
+    const auto* rec = static_cast<const uint8_t*>(d_records);
+    const auto* offs = static_cast<const uint32_t*>(d_offsets);
+    const auto* sh = static_cast<const uint8_t*>(d_shares);
+    const auto* roots = static_cast<const uint8_t*>(d_roots);
+    const auto* rrec = static_cast<const uint8_t*>(d_root_records);
+    const auto* dr = static_cast<const uint8_t*>(d_data_roots);
+    const auto* q = static_cast<const RangeQuery*>(dq);
+    const hipError_t e =
+        nmt ? launch_nmt_range_verify(rec, offs, sh, shares_total, roots, rrec, dr, width, share_size, nmt->namespace_size,
+                                      nmt->square_size, nmt->ignore_max_namespace, q, n, static_cast<uint32_t*>(d_status), st)
+            : launch_range_verify(rec, offs, sh, shares_total, roots, rrec, dr, width, share_size, q, n,
+                                  static_cast<uint32_t*>(d_status), st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "range proof verify kernel launch");
 }
 
 int stage_samples(hipStream_t st, StreamScratch& ss, const rsm_sample* samples, uint32_t n, const ProofSample** ds) {
@@ -656,6 +711,140 @@ int rsm_eds_namespace_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, i
             const uint32_t start = le32(records_out + (size_t)i * RB + 4);
             for (uint32_t p = 0; p < offsets_out[i + 1] - offsets_out[i]; ++p)
                 memcpy(shares_out + (size_t)(offsets_out[i] + p) * S, e->cell(e->rr(axis, indices[i], start + p), e->cc(axis, indices[i], start + p)), S);
+        }
+    return RSM_OK;
+}
+
+uint32_t rsm_range_record_bytes(uint32_t width, const rsm_nmt_params* nmt) {
+    if (width == 0 || (nmt && nmt->namespace_size == 0)) return 0;
+    return 16 + (2 * proof_levels(width) + 1) * (nmt ? 2 * nmt->namespace_size + 32 : 32);
+}
+
+int rsm_range_proofs_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_eds, uint32_t width, uint32_t share_size,
+                         uint32_t count, const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n,
+                         void* d_records, void* d_offsets, void* d_shares, uint64_t shares_cap, void* stream) {
+    if (!ctx || !d_nodes || width == 0 || (n && (!queries || !d_records || !d_offsets)))
+        return fail(RSM_EINVAL, "rsm_range_proofs_dev: bad arguments");
+    if (d_shares && !d_eds) return fail(RSM_EINVAL, "rsm_range_proofs_dev: d_shares needs d_eds");
+    if (d_shares && ((reinterpret_cast<uintptr_t>(d_shares) & 15u) || (reinterpret_cast<uintptr_t>(d_eds) & 15u)))
+        return fail(RSM_EINVAL, "rsm_range_proofs_dev: d_eds and d_shares must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_nodes) & 15u) || (reinterpret_cast<uintptr_t>(d_offsets) & 3u))
+        return fail(RSM_EINVAL, "rsm_range_proofs_dev: d_nodes must be 16-byte, d_offsets 4-byte aligned");
+    if (int rc = validate_chunk_size(share_size)) return rc;
+    DevTree t;
+    if (!proof_tree_for(width, nmt, &t) || rsm_proof_nodes_bytes(width, nmt, count ? count : 1) == 0)
+        return fail(RSM_EUNSUPPORTED, "rsm_range_proofs_dev: %u squares of width %u%s not supported", count, width,
+                    nmt ? " (NMT)" : "");
+    if (n > (1u << 20)) return fail(RSM_EINVAL, "rsm_range_proofs_dev: at most %u queries per call", 1u << 20);
+    if (n == 0 || count == 0) return RSM_OK;
+    if (int rc = check_range_queries("rsm_range_proofs_dev", queries, n, count, width)) return rc;
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t st = pick(ctx, stream);
+    StreamScratch& ss = stream_scratch(ctx, st);
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const void* dq = nullptr;
+    if (int rc = stage_bytes(st, ss, queries, (size_t)n * sizeof(rsm_range_query), &dq)) return rc;
+    const hipError_t e = launch_range_proofs(static_cast<const uint32_t*>(d_nodes), static_cast<const uint8_t*>(d_eds), width,
+                                             share_size, count, t.nmt ? t.p.namespace_size : 0u,
+                                             static_cast<const RangeQuery*>(dq), n, static_cast<uint8_t*>(d_records),
+                                             static_cast<uint32_t*>(d_offsets), static_cast<uint8_t*>(d_shares), shares_cap, st);
+    return e == hipSuccess ? RSM_OK : hip_fail(e, "range proof kernel launch");
+}
+
+int rsm_range_proofs_verify_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets, const void* d_shares,
+                                uint64_t shares_total, const void* d_roots, uint32_t width, uint32_t share_size,
+                                uint32_t count, const rsm_nmt_params* nmt, const rsm_range_query* queries, uint32_t n,
+                                void* d_status, void* stream) {
+    return range_verify_call("rsm_range_proofs_verify_dev", ctx, queries && d_records && d_offsets && d_roots && d_status,
+                             d_records, d_offsets, d_shares, shares_total, d_roots, nullptr, nullptr, width, share_size, count,
+                             nmt, queries, n, d_status, stream);
+}
+
+int rsm_range_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_records, const void* d_offsets, const void* d_shares,
+                                          uint64_t shares_total, const void* d_root_records, const void* d_data_roots,
+                                          uint32_t width, uint32_t share_size, uint32_t count, const rsm_nmt_params* nmt,
+                                          const rsm_range_query* queries, uint32_t n, void* d_status, void* stream) {
+    return range_verify_call("rsm_range_proofs_verify_data_root_dev", ctx,
+                             queries && d_records && d_offsets && d_root_records && d_data_roots && d_status, d_records,
+                             d_offsets, d_shares, shares_total, nullptr, d_root_records, d_data_roots, width, share_size, count,
+                             nmt, queries, n, d_status, stream);
+}
+
+int rsm_share_range_queries(uint32_t k, uint32_t square, uint32_t start, uint32_t end, rsm_range_query* queries_out,
+                            uint32_t* n_out) {
+    if (!queries_out || !n_out || k == 0 || k > 32768u || !(start < end && end <= k * k))
+        return fail(RSM_EINVAL, "rsm_share_range_queries: bad arguments (1 <= k <= 32768, start < end <= k * k)");
+    uint32_t n = 0;
+    for (uint32_t row = start / k; row * k < end; ++row) {  // k * k <= 2^30
+        const uint32_t lo = std::max(start, row * k), hi = std::min(end, (row + 1) * k);
+        queries_out[n++] = rsm_range_query{square, RSM_AXIS_ROW, row, lo - row * k, hi - row * k};
+    }
+    *n_out = n;
+    return RSM_OK;
+}
+
+int rsm_eds_range_proofs(rsm_eds* e, rsm_tree_root_fn tree_fn, void* user, const rsm_range_query* queries, uint32_t n,
+                         uint8_t* records_out, uint32_t* offsets_out, uint8_t* shares_out, uint64_t shares_cap) {
+    if (!e || !offsets_out || (n && (!queries || !records_out))) return fail(RSM_EINVAL, "rsm_eds_range_proofs: bad arguments");
+    const rsm_nmt_params* nmt = nmt_of(tree_fn, user);
+    if (!nmt && tree_fn != nullptr && tree_fn != rsm_default_tree_root)
+        return fail(RSM_EUNSUPPORTED, "rsm_eds_range_proofs: range proofs are built for the DefaultTree and the NMT only");
+    const uint32_t W = e->width, S = e->S;
+    const uint32_t RB = rsm_range_record_bytes(W, nmt);
+    if (RB == 0 || (nmt && nmt->square_size == 0))
+        return fail(RSM_EINVAL, "rsm_eds_range_proofs: empty square, namespace size or square size 0");
+    if (int rc = check_range_queries("rsm_eds_range_proofs", queries, n, 1, W)) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t p = 0; p < W; ++p)
+            if (!e->has(e->rr((int)queries[i].axis, queries[i].index, p), e->cc((int)queries[i].axis, queries[i].index, p)))
+                return fail(RSM_ETREE, "can not prove a range of incomplete %s %u", queries[i].axis == 0 ? "row" : "column",
+                            queries[i].index);
+    offsets_out[0] = 0;
+    for (uint32_t i = 0; i < n; ++i) offsets_out[i + 1] = offsets_out[i] + (queries[i].end - queries[i].start);
+    if (n == 0) return RSM_OK;
+    DevTree dt;
+    if (n <= (1u << 20) && store_path(e, nmt, &dt)) {
+        rsm_ctx* ctx = e->ctx;
+        std::lock_guard<std::mutex> lk(ctx->eds_mu);
+        if (int rc = use_device(ctx)) return rc;
+        hipStream_t st = ctx->stream;
+        hipError_t r;
+        if (int rc = ensure_store(e, nmt, dt)) return rc;
+        ProofStore& ps = e->proofs;
+        for (uint32_t i = 0; i < n; ++i)
+            if (ps.status[(size_t)queries[i].axis * W + queries[i].index])
+                return fail(RSM_ETREE, "tree error proving a range of %s %u (namespace order)",
+                            queries[i].axis == 0 ? "row" : "column", queries[i].index);
+        // offsets | records in one scratch buffer; the shares are this square's host bytes
+        const size_t o_rec = (size_t)(n + 1) * 4, total = o_rec + (size_t)n * RB;
+        DevBuf& rb = ctx->eds.scratch;
+        if ((r = rb.ensure(total)) != hipSuccess) return hip_fail(r, "hipMalloc (range proof records)");
+        auto* d = static_cast<uint8_t*>(rb.ptr);
+        if (int rc = rsm_range_proofs_dev(ctx, ps.d_nodes, nullptr, W, S, 1, nmt, queries, n, d + o_rec, d, nullptr, 0, st))
+            return rc;
+        if ((r = hipMemcpyAsync(records_out, d + o_rec, (size_t)n * RB, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(r, "D2H range proof records");
+        if ((r = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(r, "proof stream");
+    } else {
+        std::vector<const uint8_t*> leaves(W);
+        for (uint32_t i = 0; i < n; ++i) {
+            const rsm_range_query& q = queries[i];
+            for (uint32_t p = 0; p < W; ++p) leaves[p] = e->cell(e->rr((int)q.axis, q.index, p), e->cc((int)q.axis, q.index, p));
+            uint8_t* rec = records_out + (size_t)i * RB;
+            const int rc = nmt ? rsm_nmt_tree_range_prove(nmt, q.index, leaves.data(), W, S, q.start, q.end, rec, nullptr)
+                               : rsm_default_tree_range_prove(leaves.data(), W, S, q.start, q.end, rec, nullptr);
+            if (rc == RSM_ETREE)
+                return fail(RSM_ETREE, "tree error proving a range of %s %u", q.axis == 0 ? "row" : "column", q.index);
+            if (rc) return fail(rc, "rsm_eds_range_proofs: bad tree parameters");
+        }
+    }
+    if (shares_out)
+        for (uint32_t i = 0; i < n; ++i) {
+            if (offsets_out[i + 1] > shares_cap) continue;
+            const rsm_range_query& q = queries[i];
+            for (uint32_t p = q.start; p < q.end; ++p)
+                memcpy(shares_out + (size_t)(offsets_out[i] + p - q.start) * S,
+                       e->cell(e->rr((int)q.axis, q.index, p), e->cc((int)q.axis, q.index, p)), S);
         }
     return RSM_OK;
 }
