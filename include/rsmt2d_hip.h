@@ -714,6 +714,100 @@ int rsm_range_proofs_verify_data_root_dev(rsm_ctx* ctx, const void* d_records, c
 int rsm_share_range_queries(uint32_t k, uint32_t square, uint32_t start, uint32_t end,
                             rsm_range_query* queries_out /* [k] */, uint32_t* n_out);
 
+/* ---- share commitments -------------------------------------------------------------- */
+/* The 32-byte hash a MsgPayForBlobs carries for a blob: celestia-app's
+ * inclusion.CreateCommitment (from the blob's shares) and inclusion.GetCommitment (from a
+ * square's cached subtree roots).  With n >= 1 the blob's share count and t >= 1 the
+ * subtree root threshold (Celestia: 64), pow2ceil(x) the least power of two >= x:
+ *   subtree width  w(n, t) = min(pow2ceil(ceil(n / t)), pow2ceil(ceil(sqrt(n))));
+ *   mountain range sizes(n, w): while n > 0 emit w if n >= w, else the largest power of
+ *     two <= n, and subtract it -- M sizes, never increasing, each dividing the one before;
+ *   subtree root r_i: the NMT root (min || max || digest, 2 * namespace_size + 32 bytes)
+ *     over the i-th run of shares, every leaf under its own namespace share[:namespace_size]
+ *     (a run of one: the leaf node).  Within a run a namespace below its predecessor's is a
+ *     push-order error; across a run boundary it is not;
+ *   commitment: the RFC 6962 root over r_0 .. r_{M-1} (leaf SHA-256(0x00 || r_i), node
+ *     SHA-256(0x01 || l || r), split at the largest power of two below the count; M = 1
+ *     gives the leaf hash) -- tendermint's HashFromByteSlices.
+ * In a square of ODS width k (a power of two) a blob at ODS shares [start, start + len),
+ * row-major, with start a multiple of w(len, t) (the non-interactive default rules,
+ * ADR-013) has w <= k, no subtree crosses a row, and the subtree of size z at position p is
+ * node (log2 z, (p mod k) >> log2 z) of row p / k's tree in the level picture of "share
+ * inclusion proofs": the node store of rsm_proof_nodes_dev already holds it.
+ * square_size of the params is not used by the shares forms.  Only the NMT has
+ * commitments: nmt == NULL is RSM_EUNSUPPORTED. */
+#define RSM_COMMIT_ORDER 1 /* a push-order error inside a subtree; the commitment is 32 zeros */
+#define RSM_COMMIT_TREE 2  /* store forms: a touched row's tree status word is non-zero
+                              (its quadrant-0 namespaces are out of order); 32 zeros */
+/* Host helpers.  rsm_subtree_width: w(share_count, threshold), 0 for a zero argument.
+ * rsm_subtree_sizes: the M sizes into sizes_out[0 .. M) and M into *n_out; sizes_out NULL
+ * only counts.  RSM_EINVAL for share_count 0, a width that is no power of two, n_out NULL,
+ * or M > cap (then *n_out is still set and nothing is written). */
+uint32_t rsm_subtree_width(uint32_t share_count, uint32_t threshold);
+int rsm_subtree_sizes(uint32_t share_count, uint32_t width, uint32_t* sizes_out, uint32_t cap, uint32_t* n_out);
+/* Host restatements (merkle.cpp).  rsm_blob_commitment: shares [n_shares][share_size],
+ * any count, from the blob's own runs.  *status 0 with the commitment in out, or
+ * RSM_COMMIT_ORDER with zeros.  RSM_EINVAL for NULL operands, n_shares, threshold or
+ * namespace_size 0, namespace_size > 32; RSM_ETREE for shares shorter than a namespace. */
+int rsm_blob_commitment(const rsm_nmt_params* params, const uint8_t* shares, uint32_t n_shares, uint32_t share_size,
+                        uint32_t threshold, uint8_t out[32], uint32_t* status);
+/* rsm_square_commitment: the same value through the row-tree coordinates above, an
+ * independent statement.  The square is either ods (k * k share pointers, row-major) or
+ * eds ([2k][2k][share_size] bytes), exactly one non-NULL.  The levels of each touched
+ * row's quadrant-0 half are built and the blob's nodes read off; roots_out (nullable)
+ * receives the M subtree roots, packed.  *status 0, or RSM_COMMIT_TREE with zeros where a
+ * touched row's namespaces are out of order.  RSM_EINVAL also unless k is a power of two,
+ * len >= 1, start + len <= k * k and start is a multiple of w(len, threshold). */
+int rsm_square_commitment(const rsm_nmt_params* params, const uint8_t* const* ods, const uint8_t* eds, uint32_t k,
+                          uint32_t share_size, uint32_t start, uint32_t len, uint32_t threshold, uint8_t out[32],
+                          uint8_t* roots_out, uint32_t* status);
+/* Shares path, device: the commitments of n blobs in one call.  Blob i is shares
+ * [offsets[i], offsets[i + 1]) of the packed d_shares (device, 16-byte aligned).  `offsets`
+ * (n + 1 share offsets) is HOST memory, validated before anything is enqueued (RSM_EINVAL
+ * names the first blob that is empty or whose offsets decrease) and used before the call
+ * returns.  d_commitments [n][32] (any alignment) and d_status [n] uint32 (4-byte aligned)
+ * receive, per blob, the commitment and 0, or 32 zeros and RSM_COMMIT_ORDER; which
+ * subtree failed first is decided as a minimum over subtree indices, so no lane order
+ * shows.  d_work (16-byte aligned): rsm_commit_work_bytes(total shares, total subtree
+ * roots, nmt) bytes -- the leaf records, the packed subtree roots and their flags.
+ * Three stages: one lane per share (leaf records); one launch per subtree size present
+ * (size 1 a copy, 2 .. 128 packed into waves, 256 .. 1024 a workgroup each); one workgroup
+ * per blob for the fold.  Limits, RSM_EUNSUPPORTED beyond them: n <= 2^20, total shares
+ * <= 2^24, subtree width <= 1024 (the device NMT's width and LDS: 512 at namespace_size
+ * 32), at most 4096 subtree roots per blob.  rsm_commit_work_bytes is 0 for nmt == NULL, a
+ * namespace size outside 1 .. 32, more than 2^24 shares or more roots than shares.
+ * Share size rules and argument errors as rsm_range_proofs_verify_dev (a multiple of 64,
+ * else RSM_ESHARESIZE; >= namespace_size, else RSM_ETREE; RSM_EINVAL for NULL or
+ * misaligned operands, threshold 0, namespace_size outside 1 .. 32).  No address depends
+ * on what a share holds.  n == 0 launches nothing.  Asynchronous on `stream`. */
+uint64_t rsm_commit_work_bytes(uint64_t total_shares, uint64_t total_subtree_roots, const rsm_nmt_params* nmt);
+int rsm_blob_commitments_dev(rsm_ctx* ctx, const void* d_shares, uint32_t share_size, const rsm_nmt_params* nmt,
+                             uint32_t threshold, const uint32_t* offsets, uint32_t n, void* d_work, void* d_commitments,
+                             void* d_status, void* stream);
+/* Store path, device: the commitments of n blobs that sit in `count` squares whose NMT
+ * node store (d_nodes) and tree status words (d_status_trees, 2 * width per square) are
+ * what rsm_proof_nodes_dev wrote.  No share is read and no leaf is hashed: the call
+ * gathers each blob's M nodes and folds them; it takes no scratch. */
+typedef struct {
+    uint32_t square; /* square of the batch */
+    uint32_t start;  /* ODS shares [start, start + len), row-major in the k x k original square */
+    uint32_t len;
+} rsm_blob_ref;
+/* `blobs` is HOST memory, validated before anything is enqueued and copied before the call
+ * returns: RSM_EINVAL names the first blob with square >= count, len == 0, start + len >
+ * k * k or start not a multiple of w(len, threshold).  RSM_EUNSUPPORTED unless k =
+ * width / 2 is a power of two and the store's own limits hold (rsm_proof_nodes_bytes != 0),
+ * for n > 2^20 and for a blob of more than 4096 subtree roots.  d_status [n]: 0, or
+ * RSM_COMMIT_TREE (a touched row's status word is non-zero) with 32 zeros in
+ * d_commitments [n][32] (any alignment).  d_roots_out (nullable, any alignment) receives
+ * the subtree roots of all blobs, packed, 2 * namespace_size + 32 bytes each -- the
+ * SubtreeRoots of a commitment proof -- and d_root_offsets (nullable, 4-byte aligned) the
+ * n + 1 root offsets.  Exactly n commitments and n status words are written, plus the
+ * optional outputs.  n == 0 or count == 0 launches nothing.  Asynchronous on `stream`. */
+int rsm_commitments_dev(rsm_ctx* ctx, const void* d_nodes, const void* d_status_trees, uint32_t width, uint32_t count,
+                        const rsm_nmt_params* nmt, uint32_t threshold, const rsm_blob_ref* blobs, uint32_t n,
+                        void* d_roots_out, void* d_root_offsets, void* d_commitments, void* d_status, void* stream);
+
 /* ---- ExtendedDataSquare (extendeddatasquare.go, datasquare.go) ------------------ */
 /* ComputeExtendedDataSquare(data, codec, tree) (:50-77): n shares (lens[i] bytes). */
 int rsm_eds_compute(rsm_ctx* ctx, const uint8_t* const* data, const uint32_t* lens, uint64_t n,
@@ -790,6 +884,22 @@ int rsm_eds_namespace_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user,
  * query.  Results never depend on the path. */
 int rsm_eds_range_proofs(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_range_query* queries, uint32_t n,
                          uint8_t* records_out, uint32_t* offsets_out, uint8_t* shares_out, uint64_t shares_cap);
+
+/* Share commitments ("share commitments" above) of n blobs (square = 0) of this square:
+ * out [n][32], status_out [n] (0 or RSM_COMMIT_TREE with zeros).  tree_fn / user must be
+ * rsm_nmt_tree_root with its params, square_size the square's ODS width (any other plugin
+ * RSM_EUNSUPPORTED).  RSM_EINVAL names the first blob that rsm_commitments_dev would
+ * refuse; RSM_ETREE for a blob that touches a nil quadrant-0 cell.  With a context, a
+ * complete square and a supported width the cached node store of rsm_eds_proofs is reused
+ * or built and one rsm_commitments_dev call answers; otherwise rsm_square_commitment runs
+ * per blob.  Results never depend on the path.  rsm_eds_subtree_roots: the same call that
+ * also hands out the blobs' subtree roots, packed (roots_out, room for the sum of their
+ * counts -- rsm_subtree_sizes), and the n + 1 root offsets (root_offsets_out). */
+int rsm_eds_commitments(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_blob_ref* blobs, uint32_t n,
+                        uint32_t threshold, uint8_t* out, uint32_t* status_out);
+int rsm_eds_subtree_roots(rsm_eds* eds, rsm_tree_root_fn tree_fn, void* user, const rsm_blob_ref* blobs, uint32_t n,
+                          uint32_t threshold, uint8_t* out, uint32_t* status_out, uint8_t* roots_out,
+                          uint32_t* root_offsets_out);
 
 /* Rebuilding a square from sampled shares: verifies n samples (square = 0; shares
  * [n][share size], records [n][rsm_proof_record_bytes(width, nmt)]) against the

@@ -45,6 +45,8 @@ __all__ = [
     "verify_fraud_proofs_dev", "BadEncodingProof",
     "RangeQuery", "RangeProof", "ShareProof", "share_range_queries", "prove_ranges_dev", "verify_ranges_dev",
     "verify_ranges_data_root_dev",
+    "RSM_COMMIT_ORDER", "RSM_COMMIT_TREE", "BlobRef", "SubTreeWidth", "MerkleMountainRangeSizes", "CreateCommitment",
+    "blob_commitments_dev", "commitments_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +64,8 @@ RSM_ENOMEM, RSM_EUNSUPPORTED, RSM_EUNREPAIRABLE, RSM_EBYZANTINE, RSM_ECELL, RSM_
 RSM_PROOF_OK, RSM_PROOF_MALFORMED, RSM_PROOF_ORDER, RSM_PROOF_ROOT, RSM_PROOF_OCCUPIED = 0, 1, 2, 3, 4
 # namespace proofs only: a share of another namespace / shares of the namespace left out
 RSM_PROOF_NAMESPACE, RSM_PROOF_INCOMPLETE = 5, 6
+# share commitment status words (one per blob)
+RSM_COMMIT_ORDER, RSM_COMMIT_TREE = 1, 2
 
 
 class RSMError(Exception):
@@ -276,6 +280,17 @@ SIGNATURES = {
                                                      ctypes.POINTER(NmtParams), _VP, _U32, _VP, _VP]),
     "rsm_share_range_queries": (_I32, [_U32, _U32, _U32, _U32, _VP, ctypes.POINTER(_U32)]),
     "rsm_eds_range_proofs": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _U64]),
+    "rsm_subtree_width": (_U32, [_U32, _U32]),
+    "rsm_subtree_sizes": (_I32, [_U32, _U32, _VP, _U32, ctypes.POINTER(_U32)]),
+    "rsm_blob_commitment": (_I32, [ctypes.POINTER(NmtParams), _VP, _U32, _U32, _U32, _VP, ctypes.POINTER(_U32)]),
+    "rsm_square_commitment": (_I32, [ctypes.POINTER(NmtParams), _VP, _VP, _U32, _U32, _U32, _U32, _U32, _VP, _VP,
+                                     ctypes.POINTER(_U32)]),
+    "rsm_commit_work_bytes": (_U64, [_U64, _U64, ctypes.POINTER(NmtParams)]),
+    "rsm_blob_commitments_dev": (_I32, [_VP, _VP, _U32, ctypes.POINTER(NmtParams), _U32, _VP, _U32, _VP, _VP, _VP, _VP]),
+    "rsm_commitments_dev": (_I32, [_VP, _VP, _VP, _U32, _U32, ctypes.POINTER(NmtParams), _U32, _VP, _U32, _VP, _VP, _VP, _VP,
+                                   _VP]),
+    "rsm_eds_commitments": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _VP]),
+    "rsm_eds_subtree_roots": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _VP]),
     "rsm_eds_namespace_proofs": (_I32, [_VP, _VP, _VP, _I32, _VP, _U32, _VP, _VP, _VP, _VP, _U64]),
     "rsm_eds_import_samples": (_I32, [_VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, ctypes.POINTER(_U32)]),
     "rsm_data_root_record_bytes": (_U32, [_U32]),
@@ -1406,6 +1421,123 @@ def verify_ranges_data_root_dev(records: "DeviceBuffer", offsets: "DeviceBuffer"
                           [root_records, data_roots], width, share_size, queries, nmt, count)
 
 
+# ---------------------------------------------------------------------------
+# Share commitments (include/rsmt2d_hip.h "share commitments")
+# ---------------------------------------------------------------------------
+class BlobRef(ctypes.Structure):
+    """rsm_blob_ref: ODS shares [start, start + len) of ``square``, row-major."""
+    _fields_ = [("square", ctypes.c_uint32), ("start", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+def SubTreeWidth(shareCount: int, subtreeRootThreshold: int = 64) -> int:
+    """celestia-app's inclusion.SubTreeWidth (rsm_subtree_width)."""
+    return int(library().rsm_subtree_width(shareCount, subtreeRootThreshold))
+
+
+def MerkleMountainRangeSizes(totalSize: int, maxTreeSize: int) -> List[int]:
+    """celestia-app's inclusion.MerkleMountainRangeSizes (rsm_subtree_sizes)."""
+    if totalSize == 0:
+        return []
+    L, m = library(), ctypes.c_uint32(0)
+    _check(L.rsm_subtree_sizes(totalSize, maxTreeSize, None, 0, ctypes.byref(m)))
+    out = (ctypes.c_uint32 * m.value)()
+    _check(L.rsm_subtree_sizes(totalSize, maxTreeSize, out, m.value, ctypes.byref(m)))
+    return list(out)
+
+
+def _commit_error(status: int) -> RSMError:
+    return RSMError(RSM_ETREE, "share commitment: namespaces out of order (status %d)" % status)
+
+
+def blob_commitments_dev(shares: "DeviceBuffer", share_size: int, offsets: Sequence[int], nmt: NmtParams,
+                         threshold: int = 64):
+    """(commitments [n][32], status words [n]) of the n blobs whose shares are
+    [offsets[i], offsets[i + 1]) of the packed device-resident ``shares``: one
+    rsm_blob_commitments_dev call (leaf pass, subtree pass, fold)."""
+    import numpy as np
+    L, ctx, n = library(), shares.ctx, len(offsets) - 1
+    com, st = np.zeros((max(n, 0), 32), np.uint8), np.zeros(max(n, 0), np.uint32)
+    if n <= 0:
+        return com, st
+    offs = (ctypes.c_uint32 * (n + 1))(*[int(o) for o in offsets])
+    lens = [int(offsets[i + 1]) - int(offsets[i]) for i in range(n)]
+    total = int(offsets[n]) - int(offsets[0])
+    roots = sum(len(MerkleMountainRangeSizes(x, SubTreeWidth(x, threshold))) for x in lens if x > 0)
+    wb = int(L.rsm_commit_work_bytes(max(total, 0), roots, _nmt_ref(nmt)))
+    bufs = [DeviceBuffer(max(wb, 16)), DeviceBuffer(n * 32), DeviceBuffer(n * 4)]
+    work, dc, ds = bufs
+    try:
+        _check(L.rsm_blob_commitments_dev(ctx, shares.ptr, share_size, _nmt_ref(nmt), threshold, offs, n, work.ptr, dc.ptr,
+                                          ds.ptr, None))
+        _check(L.rsm_sync(ctx))
+        com[:] = dc.download(n * 32).reshape(n, 32)
+        st[:] = ds.download(n * 4).view(np.uint32)
+    finally:
+        for b in bufs:
+            b.free()
+    return com, st
+
+
+def commitments_dev(nodes: "DeviceBuffer", status_trees: "DeviceBuffer", width: int, blobs: Sequence[tuple], nmt: NmtParams,
+                    threshold: int = 64, count: int = 1, want_roots: bool = False):
+    """(commitments [n][32], status words [n]) of ``(square, start, len)`` blobs out of the
+    NMT node store and tree status words rsm_proof_nodes_dev wrote: one rsm_commitments_dev
+    call, no share read.  ``want_roots``: also each blob's list of subtree roots."""
+    import numpy as np
+    L, ctx, n = library(), nodes.ctx, len(blobs)
+    com, st = np.zeros((n, 32), np.uint8), np.zeros(n, np.uint32)
+    if n == 0:
+        return (com, st, []) if want_roots else (com, st)
+    nl = 2 * nmt.namespace_size + 32
+    counts = [len(MerkleMountainRangeSizes(int(b[2]), SubTreeWidth(int(b[2]), threshold))) for b in blobs]
+    bufs = [DeviceBuffer(n * 32), DeviceBuffer(n * 4)]
+    if want_roots:
+        bufs += [DeviceBuffer(max(sum(counts) * nl, 16)), DeviceBuffer((n + 1) * 4)]
+    try:
+        _check(L.rsm_commitments_dev(ctx, nodes.ptr, status_trees.ptr, width, count, _nmt_ref(nmt), threshold,
+                                     _records(BlobRef, blobs), n, bufs[2].ptr if want_roots else None,
+                                     bufs[3].ptr if want_roots else None, bufs[0].ptr, bufs[1].ptr, None))
+        _check(L.rsm_sync(ctx))
+        com[:] = bufs[0].download(n * 32).reshape(n, 32)
+        st[:] = bufs[1].download(n * 4).view(np.uint32)
+        if want_roots:
+            offs = bufs[3].download((n + 1) * 4).view(np.uint32)
+            raw = bufs[2].download(max(sum(counts) * nl, 16)).tobytes()
+            roots = [[raw[j * nl:(j + 1) * nl] for j in range(int(offs[i]), int(offs[i + 1]))] for i in range(n)]
+            return com, st, roots
+    finally:
+        for b in bufs:
+            b.free()
+    return com, st
+
+
+def CreateCommitment(shares: Sequence[bytes], nmt: NmtParams, threshold: int = 64, device: Optional[int] = 0) -> bytes:
+    """celestia-app's inclusion.CreateCommitment over a blob's shares: the 32-byte share
+    commitment of a MsgPayForBlobs.  On the GPU (rsm_blob_commitments_dev); with
+    ``device=None`` the host restatement (rsm_blob_commitment).  Raises RSMError(RSM_ETREE)
+    where a subtree's namespaces are out of order."""
+    import numpy as np
+    n, S = len(shares), len(shares[0]) if shares else 0
+    if n == 0 or any(len(s) != S for s in shares):
+        raise RSMError(RSM_EINVAL, "CreateCommitment: a blob is one or more shares of one size")
+    flat = b"".join(shares)
+    if device is None:
+        out, st = ctypes.create_string_buffer(32), ctypes.c_uint32(0)
+        _check(library().rsm_blob_commitment(_nmt_ref(nmt), flat, n, S, threshold, out, ctypes.byref(st)))
+        if st.value:
+            raise _commit_error(st.value)
+        return out.raw
+    buf = DeviceBuffer(max(len(flat), 16), device)
+    try:
+        buf.upload(np.frombuffer(flat, np.uint8))
+        com, st = blob_commitments_dev(buf, S, [0, n], nmt, threshold)
+    finally:
+        buf.free()
+    if st[0]:
+        raise _commit_error(int(st[0]))
+    return com[0].tobytes()
+
+
 class ShareProof:
     """ODS shares [start, end) of a square under its data root (Celestia's ShareProof): per
     touched row a ``RangeProof`` and the ``RootProof`` of that row's root; ``row_roots``:
@@ -1743,6 +1875,34 @@ class ExtendedDataSquare:
         proofs = self.RangeProofs([q[1:] for q in rows])
         roots = self.RowRoots()
         return ShareProof(start, end, proofs, [self.RootProof(Row, q[2]) for q in rows], [roots[q[2]] for q in rows])
+
+    # --- share commitments (rsm_eds_commitments, rsm_eds_subtree_roots) ---
+    def _commit(self, start: int, length: int, threshold: int):
+        tf = self._tree_fn
+        if not isinstance(tf, ErasuredNamespacedMerkleTreeConstructor):
+            raise RSMError(RSM_EUNSUPPORTED, "share commitments are built for the NMT only")
+        keep, fn, user = _tree_callback(tf)
+        m = len(MerkleMountainRangeSizes(length, SubTreeWidth(length, threshold))) if length > 0 and threshold > 0 else 0
+        nl = 2 * tf.params.namespace_size + 32
+        out, st = ctypes.create_string_buffer(32), (ctypes.c_uint32 * 1)()
+        roots, offs = ctypes.create_string_buffer(max(m * nl, 1)), (ctypes.c_uint32 * 2)()
+        _check(library().rsm_eds_subtree_roots(self._h, fn, user, _records(BlobRef, [(0, start, length)]), 1, threshold, out,
+                                               st, roots, offs))
+        if st[0]:
+            raise _commit_error(int(st[0]))
+        return out.raw, [roots.raw[i * nl:(i + 1) * nl] for i in range(m)]
+
+    def Commitment(self, start: int, length: int, threshold: int = 64) -> bytes:
+        """The share commitment of the blob at ODS shares [start, start + length), read off
+        the row trees' cached nodes (celestia-app's inclusion.GetCommitment); ``start`` is
+        a multiple of ``SubTreeWidth(length, threshold)``.  Equals ``CreateCommitment`` of
+        those shares."""
+        return self._commit(start, length, threshold)[0]
+
+    def SubtreeRoots(self, start: int, length: int, threshold: int = 64) -> List[bytes]:
+        """The blob's subtree roots (min || max || digest each): inner nodes of the row
+        trees, the SubtreeRoots of a commitment proof."""
+        return self._commit(start, length, threshold)[1]
 
     def NamespaceData(self, nid: bytes) -> List[tuple]:
         """``(rowIdx, NamespaceProof)`` for every row whose proof for ``nid`` is not

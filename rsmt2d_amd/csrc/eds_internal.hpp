@@ -119,6 +119,16 @@ struct ProofStore {
     }
 };
 
+namespace rsm {
+// The cached node store of a square, for the entry points outside rsm_proof.cpp
+// (rsm_commit.cpp): the NMT params of (tree_fn, user) or nullptr; whether a complete square
+// with a context takes the device path for tree `nmt`; the store itself, built once
+// (ctx->eds_mu held, device selected).
+const rsm_nmt_params* eds_nmt_of(rsm_tree_root_fn tree_fn, void* user);
+bool eds_store_path(rsm_eds* e, const rsm_nmt_params* nmt, DevTree* dt);
+int eds_ensure_store(rsm_eds* e, const rsm_nmt_params* nmt, const DevTree& dt);
+}  // namespace rsm
+
 struct rsm_eds {
     rsm_ctx* ctx = nullptr;
     uint32_t width = 0;

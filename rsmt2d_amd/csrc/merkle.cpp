@@ -1111,3 +1111,139 @@ extern "C" int rsm_nmt_tree_range_verify(const rsm_nmt_params* p, uint32_t index
     *status = memcmp(cur.data(), root, NB) == 0 ? RSM_PROOF_OK : RSM_PROOF_ROOT;
     return RSM_OK;
 }
+
+// ---- share commitments (include/rsmt2d_hip.h "share commitments") ----
+// Host restatements of kernels_commit.hip, stated twice: rsm_blob_commitment from the
+// blob's own runs (an NMT per run, every leaf under its own namespace), and
+// rsm_square_commitment from the levels of the touched rows' trees, read at the
+// coordinates the blob's place in the square dictates.  The RFC 6962 root over the
+// subtree roots is the DefaultTree over them.
+namespace {
+
+uint64_t pow2ceil64(uint64_t x) {
+    uint64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+// The RFC 6962 root over M roots of NB bytes (tendermint's HashFromByteSlices).
+int commitment_of(const std::vector<uint8_t>& roots, uint32_t M, uint32_t NB, uint8_t out[32]) {
+    std::vector<const uint8_t*> ptrs(M);
+    for (uint32_t i = 0; i < M; ++i) ptrs[i] = &roots[(size_t)i * NB];
+    uint32_t len = 32;
+    return rsm_default_tree_root(nullptr, 0, 0, ptrs.data(), M, NB, out, &len);
+}
+
+}  // namespace
+
+extern "C" uint32_t rsm_subtree_width(uint32_t share_count, uint32_t threshold) {
+    if (share_count == 0 || threshold == 0) return 0;
+    const uint64_t by_threshold = pow2ceil64(((uint64_t)share_count + threshold - 1) / threshold);
+    uint64_t s = 1;  // ceil(sqrt(share_count))
+    while (s * s < share_count) ++s;
+    return (uint32_t)std::min(by_threshold, pow2ceil64(s));
+}
+
+extern "C" int rsm_subtree_sizes(uint32_t share_count, uint32_t width, uint32_t* sizes_out, uint32_t cap, uint32_t* n_out) {
+    if (!n_out || share_count == 0 || width == 0 || (width & (width - 1))) return RSM_EINVAL;
+    uint32_t m = share_count / width;
+    for (uint32_t rem = share_count % width; rem; rem &= rem - 1) ++m;
+    *n_out = m;
+    if (!sizes_out) return RSM_OK;
+    if (m > cap) return RSM_EINVAL;
+    uint32_t i = 0;
+    for (uint32_t n = share_count; n > 0;) {
+        uint32_t z = width;
+        while (z > n) z >>= 1;  // the largest power of two <= n
+        sizes_out[i++] = z;
+        n -= z;
+    }
+    return RSM_OK;
+}
+
+extern "C" int rsm_blob_commitment(const rsm_nmt_params* p, const uint8_t* shares, uint32_t n_shares, uint32_t share_size,
+                                   uint32_t threshold, uint8_t out[32], uint32_t* status) {
+    if (!p || !shares || !out || !status || n_shares == 0 || threshold == 0 || p->namespace_size == 0 ||
+        p->namespace_size > 32)
+        return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32;
+    if (share_size < nsz) return RSM_ETREE;  // data is too short to contain namespace ID
+    const uint32_t w = rsm_subtree_width(n_shares, threshold);
+    std::vector<uint8_t> roots;
+    std::vector<const uint8_t*> leaves;
+    uint32_t M = 0;
+    for (uint32_t at = 0; at < n_shares; ++M) {
+        uint32_t z = w;
+        while (z > n_shares - at) z >>= 1;
+        // the run's own tree: a wrapper over z leaves whose every leaf is in quadrant 0
+        rsm_nmt_params run{nsz, p->ignore_max_namespace, z};
+        leaves.resize(z);
+        for (uint32_t i = 0; i < z; ++i) leaves[i] = shares + (size_t)(at + i) * share_size;
+        roots.resize((size_t)(M + 1) * NB);
+        uint32_t len = NB;
+        const int rc = rsm_nmt_tree_root(&run, 0, 0, leaves.data(), z, share_size, &roots[(size_t)M * NB], &len);
+        if (rc == RSM_ETREE) {
+            memset(out, 0, 32);
+            *status = RSM_COMMIT_ORDER;
+            return RSM_OK;
+        }
+        if (rc) return rc;
+        at += z;
+    }
+    *status = 0;
+    return commitment_of(roots, M, NB, out);
+}
+
+extern "C" int rsm_square_commitment(const rsm_nmt_params* p, const uint8_t* const* ods, const uint8_t* eds, uint32_t k,
+                                     uint32_t share_size, uint32_t start, uint32_t len, uint32_t threshold, uint8_t out[32],
+                                     uint8_t* roots_out, uint32_t* status) {
+    if (!p || !out || !status || (ods == nullptr) == (eds == nullptr) || k == 0 || (k & (k - 1)) || k > 32768u ||
+        threshold == 0 || len == 0 || p->namespace_size == 0 || p->namespace_size > 32)
+        return RSM_EINVAL;
+    if ((uint64_t)start + len > (uint64_t)k * k) return RSM_EINVAL;
+    const uint32_t w = rsm_subtree_width(len, threshold);
+    if (start % w) return RSM_EINVAL;
+    const uint32_t nsz = p->namespace_size, NB = 2 * nsz + 32;
+    const bool ig = p->ignore_max_namespace != 0;
+    if (share_size < nsz) return RSM_ETREE;
+    const rsm_nmt_params half{nsz, p->ignore_max_namespace, k};  // the row's quadrant-0 half: k leaves of their own
+    uint32_t top = 0;                                             // levels 0 .. log2 w are read
+    while ((1u << top) < w) ++top;
+    std::vector<std::vector<uint8_t>> lv(top + 1);
+    std::vector<const uint8_t*> leaves(k);
+    std::vector<uint8_t> roots;
+    uint32_t M = 0, have_row = ~0u;
+    for (uint32_t at = start; at < start + len; ++M) {
+        uint32_t z = w;
+        while (z > start + len - at) z >>= 1;
+        const uint32_t row = at / k, col = at % k;
+        if (row != have_row) {
+            for (uint32_t c = 0; c < k; ++c) {
+                leaves[c] = ods ? ods[(size_t)row * k + c] : eds + ((size_t)row * 2 * k + c) * share_size;
+                if (!leaves[c]) return RSM_ETREE;
+            }
+            if (nmt_leaf_level(&half, 0, leaves.data(), k, share_size, lv[0]) != RSM_OK) {  // namespace order
+                memset(out, 0, 32);
+                *status = RSM_COMMIT_TREE;
+                return RSM_OK;
+            }
+            for (uint32_t l = 1; l <= top; ++l) {
+                lv[l].assign((size_t)(k >> l) * NB, 0);
+                if (!nmt_join_pairs(lv[l - 1].data(), k >> l, lv[l].data(), nsz, ig)) {
+                    memset(out, 0, 32);
+                    *status = RSM_COMMIT_TREE;
+                    return RSM_OK;
+                }
+            }
+            have_row = row;
+        }
+        uint32_t level = 0;
+        while ((1u << level) < z) ++level;
+        roots.resize((size_t)(M + 1) * NB);
+        memcpy(&roots[(size_t)M * NB], &lv[level][(size_t)(col >> level) * NB], NB);
+        at += z;
+    }
+    if (roots_out) memcpy(roots_out, roots.data(), roots.size());
+    *status = 0;
+    return commitment_of(roots, M, NB, out);
+}

@@ -485,6 +485,45 @@ hipError_t launch_fraud_trees(const uint8_t* d_shares, const uint32_t* d_have, c
 hipError_t launch_fraud_verdicts(const uint8_t* d_present, const uint32_t* d_have, const uint32_t* d_status,
                                  const uint32_t* d_tree, const uint32_t* d_slot, const uint32_t* d_parity, uint32_t W,
                                  uint32_t n, uint32_t* out, hipStream_t st);
+// ---- share commitments (DESIGN.md §4 "Commitments"; kernels_commit.hip) ----------------
+// A blob's commitment: the RFC 6962 root (leaf SHA256(0x00 || root), node
+// SHA256(0x01 || l || r)) over its subtree roots, the NMT roots (min || max || digest,
+// 2 ns + 32 bytes, every leaf under its own namespace) over the runs of its mountain range.
+constexpr uint32_t kCommitOrder = 1, kCommitTree = 2;  // status words (the C ABI's RSM_COMMIT_*)
+constexpr uint32_t kCommitMaxRoots = 4096;             // subtree roots of one blob: the fold's LDS
+constexpr uint32_t kCommitWaveMax = 128;               // subtrees up to this size take the wave form
+// A subtree of the shares path: its first leaf record and its slot among the packed roots.
+struct CommitTask {
+    uint32_t first, slot;
+};
+// A blob of the store path: ODS shares [start, start + len) of `square`, subtree width w,
+// m subtree roots whose packed slots begin at root_off.
+struct CommitBlob {
+    uint32_t square, start, len, w, root_off, m;
+};
+// Whether the subtree pass takes subtrees of z leaves (a power of two; above
+// kCommitWaveMax the workgroup tree's limits, nmt_dev_supported).
+bool commit_subtree_supported(uint32_t z, uint32_t ns);
+// d_leaf [total][16] words: the leaf record of each of `total` packed shares (16-byte
+// aligned, S a multiple of 64 and >= ns) under the share's own namespace.
+hipError_t launch_commit_leaves(const uint8_t* d_shares, uint32_t total, uint32_t S, uint32_t ns, uint32_t* d_leaf,
+                                hipStream_t st);
+// n_tasks subtrees of z leaves each: root bytes at d_roots + slot * (2 ns + 32), the
+// slot's word of d_flags non-zero where the subtree's namespaces are out of order.
+hipError_t launch_commit_subtrees(const uint32_t* d_leaf, const CommitTask* d_tasks, uint32_t n_tasks, uint32_t z,
+                                  uint32_t ns, uint32_t ignore_max, uint8_t* d_roots, uint32_t* d_flags, hipStream_t st);
+// One workgroup per blob: blob b's roots are slots [d_root_offs[b], d_root_offs[b + 1]),
+// at most max_m <= kCommitMaxRoots of them.  d_commitments [n][32] (any alignment; zeros
+// with status kCommitOrder where a flag of the blob is set), d_status [n].
+hipError_t launch_commit_fold(const uint8_t* d_roots, const uint32_t* d_flags, const uint32_t* d_root_offs, uint32_t n,
+                              uint32_t max_m, uint32_t ns, uint8_t* d_commitments, uint32_t* d_status, hipStream_t st);
+// The same over roots gathered from an NMT node store of `squares` squares of width W
+// (d_status_trees: 2W words per square; a touched row's non-zero word gives kCommitTree and
+// zeros).  Blobs validated on the host.  d_roots_out (nullable, any alignment) receives the
+// roots at their packed slots, d_root_offs_out (nullable) the n + 1 slot offsets.
+hipError_t launch_commit_fold_store(const uint32_t* d_store, const uint32_t* d_status_trees, uint32_t W, uint32_t squares,
+                                    uint32_t ns, const CommitBlob* d_blobs, uint32_t n, uint32_t max_m, uint8_t* d_roots_out,
+                                    uint32_t* d_root_offs_out, uint8_t* d_commitments, uint32_t* d_status, hipStream_t st);
 hipError_t launch_fill_random(void* p, uint64_t bytes, uint64_t seed, hipStream_t st);
 hipError_t launch_compare(const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t* mismatch, hipStream_t st);
 // dst = src for ceil(bytes / 16) 16-byte words (src: e.g. a pinned buffer's device mapping)

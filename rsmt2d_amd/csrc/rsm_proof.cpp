@@ -233,6 +233,12 @@ int ensure_store(rsm_eds* e, const rsm_nmt_params* nmt, const DevTree& dt) {
 
 }  // namespace
 
+namespace rsm {
+const rsm_nmt_params* eds_nmt_of(rsm_tree_root_fn tree_fn, void* user) { return nmt_of(tree_fn, user); }
+bool eds_store_path(rsm_eds* e, const rsm_nmt_params* nmt, DevTree* dt) { return store_path(e, nmt, dt); }
+int eds_ensure_store(rsm_eds* e, const rsm_nmt_params* nmt, const DevTree& dt) { return ensure_store(e, nmt, dt); }
+}  // namespace rsm
+
 extern "C" {
 
 uint64_t rsm_proof_nodes_bytes(uint32_t width, const rsm_nmt_params* nmt, uint32_t count) {
