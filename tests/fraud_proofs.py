@@ -146,7 +146,7 @@ def unordered_q0(k, S, ns, seed):
 
 
 # ---- the device call -----------------------------------------------------------------
-def run(lib, proofs, table, k, S, p=None, fill=D.FILL, record_fill=0x3C):
+def run(lib, proofs, table, k, S, p=None, fill=D.FILL, record_fill=0x3C, stream=None):
     """One rsm_fraud_proofs_verify_dev over `proofs` against `table`.  d_shares, d_present,
     d_records and d_work lie between guard bands; absent slots hold `fill` shares and
     `record_fill` records.  The bands, d_present, d_records and every present slot must come
@@ -178,7 +178,7 @@ def run(lib, proofs, table, k, S, p=None, fill=D.FILL, record_fill=0x3C):
         refs = (R.RootRef * n)(*[R.RootRef(*f.ref) for f in proofs])
         out = (R.FraudVerdict * n)()
         R._check(lib.rsm_fraud_proofs_verify_dev(ctx, d_sh.ptr, d_pr.ptr, d_rec.ptr, d_roots.ptr, k, S, table.shape[0], pp,
-                                                 refs, n, d_work.ptr, out, None))
+                                                 refs, n, d_work.ptr, out, stream))
         got = d_sh.result().reshape(n, W, S).copy()
         assert np.array_equal(d_pr.result().reshape(n, W), pr), "d_present was written"
         assert np.array_equal(d_rec.result().reshape(n, W, rb), rec), "d_records was written"
@@ -192,10 +192,10 @@ def run(lib, proofs, table, k, S, p=None, fill=D.FILL, record_fill=0x3C):
     return [(v.verdict, v.reason, v.pos, v.present) for v in out], got
 
 
-def check(lib, proofs, table, k, S, p=None):
+def check(lib, proofs, table, k, S, p=None, stream=None):
     """The device against the model, record for record; the rebuilt missing slots against
     the model's vector for VALID and CONSISTENT proofs.  Returns the records."""
-    got, after = run(lib, proofs, table, k, S, p)
+    got, after = run(lib, proofs, table, k, S, p, stream=stream)
     for i, f in enumerate(proofs):
         want, full = f.expect(table, k, p)
         assert got[i] == want, (i, f.label, f.ref, got[i], want)

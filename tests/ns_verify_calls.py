@@ -41,8 +41,8 @@ def fill(g, data):
         g.buf.upload(a, offset=g.front)
 
 
-def device_ns_statuses(lib, items, W, p, roots, rec_skew=3, offsets=None, shares_total=None, n=None, count=None):
-    """One rsm_ns_proofs_verify_dev call over `items`; the status words.  Records sit
+def device_ns_statuses(lib, items, W, p, roots, rec_skew=3, offsets=None, shares_total=None, n=None, count=None, S=S):
+    """One rsm_ns_proofs_verify_dev call over `items` (shares of S bytes); the status words.  Records sit
     `rec_skew` bytes past a 64-byte boundary; d_status lies between guard bands.  `offsets`
     / `shares_total` / `n` / `count` override what the items dictate (framing tests)."""
     ns = int(p.namespace_size)
@@ -107,7 +107,7 @@ def proved(lib, p, name, q, leaves, nid):
     return Item(name, q, nid, rec, leaves[start:end] if kind == H.INCLUSION else [], root)
 
 
-def with_variants(lib, p, it, leaves, W):
+def with_variants(lib, p, it, leaves, W, S=S):
     """The item (0), its first share with one bit flipped (3; ABSENCE: the leaf node's
     digest) and the range narrowed by its first share (6)."""
     ns, k, ig = int(p.namespace_size), int(p.square_size), bool(p.ignore_max_namespace)

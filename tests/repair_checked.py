@@ -226,12 +226,12 @@ def roots_of(k, tree="default"):
 
 
 @functools.lru_cache(maxsize=None)
-def late_culprit(k, tree="default", min_round=3):
-    """(square, presence, rr, cr, outcome): the avalanche map at k on its valid square with
-    one given cell altered (one byte, past the namespace) under the original roots -- the
+def late_culprit(k, tree="default", min_round=3, S=64):
+    """(square, presence, rr, cr, outcome): the avalanche map at k on its valid square of S-byte
+    shares with one given cell altered (one byte, past the namespace) under the original roots -- the
     first seed in 0..255 (the seed picks the cell) for which the model names a vector in
     round >= min_round."""
-    valid, rr, cr = P.square_for("avalanche", k, 64, tree)
+    valid, rr, cr = P.square_for("avalanche", k, S, tree)
     pres = np.array(P.presence("avalanche", k), bool)
     given = np.flatnonzero(pres.reshape(-1))
     W = 2 * k
@@ -278,7 +278,7 @@ class Checked:
         return self.axis, self.index, self.round, self.reason, self.checked_vectors, self.hashed_cells
 
 
-def repair_checked(lib, squares, presences, roots, k, S, nmt=None, table=None):
+def repair_checked(lib, squares, presences, roots, k, S, nmt=None, table=None, stream=None):
     """One rsm_repair_squares_checked_dev over the batch, operands as repair_dev_calls.repair
     (squares between guard bands, absent cells D.FILL; table: the roots as bytes instead of
     `roots`), then one rsm_vectors_gather_dev of the named vectors.  Given cells must come
@@ -302,7 +302,7 @@ def repair_checked(lib, squares, presences, roots, k, S, nmt=None, table=None):
         d_roots.upload(table)
         res, chk = (R.RepairResult * count)(), (R.RepairCheck * count)()
         R._check(lib.rsm_repair_squares_checked_dev(ctx, d_eds.ptr, d_pres.ptr, k, S, count, pp, d_roots.ptr, d_work.ptr,
-                                                    res, chk, None))
+                                                    res, chk, stream))
         bad = [s for s in range(count) if res[s].status == BYZANTINE]
         shares = present = None
         if bad:
@@ -310,8 +310,8 @@ def repair_checked(lib, squares, presences, roots, k, S, nmt=None, table=None):
             d_sh, d_pr = Guarded(len(bad) * W * S, 0, 24), Guarded(len(bad) * W, 5, 25)
             extra += [d_sh, d_pr]
             R._check(lib.rsm_vectors_gather_dev(ctx, d_eds.ptr, d_pres.ptr, k, S, count, refs, len(bad), d_sh.ptr, d_pr.ptr,
-                                                None))
-            R._check(lib.rsm_sync(ctx))
+                                                stream))
+            R._check(lib.rsm_stream_check(ctx, stream))
             shares = d_sh.result().reshape(len(bad), W, S).copy()
             present = d_pr.result().reshape(len(bad), W).copy()
         got = d_eds.result().reshape(count, W, W, S).copy()

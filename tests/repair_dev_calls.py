@@ -58,10 +58,11 @@ class Result:
         return self.status, self.sweeps, self.vectors, self.missing
 
 
-def repair(lib, squares, presences, roots, k, S, nmt=None, ctx=None):
+def repair(lib, squares, presences, roots, k, S, nmt=None, ctx=None, stream=None):
     """One rsm_repair_squares_dev over the batch: squares [W][W][S] uint8 (as given()),
     presences [W][W] bool, roots [(rr, cr)].  d_eds, d_presence and d_work lie between
-    guard bands, which must come back intact, and every given cell byte-identical.
+    guard bands, which must come back intact, and every given cell byte-identical.  `stream`:
+    the caller stream the call runs on (NULL: the context stream).
     Returns one Result per square."""
     ctx = R.device_context(0) if ctx is None else ctx
     count, W = len(squares), 2 * k
@@ -80,7 +81,7 @@ def repair(lib, squares, presences, roots, k, S, nmt=None, ctx=None):
         d_pres.buf.upload(pres.reshape(-1), d_pres.front)
         d_roots.upload(table)
         res = (R.RepairResult * count)()
-        R._check(lib.rsm_repair_squares_dev(ctx, d_eds.ptr, d_pres.ptr, k, S, count, pp, d_roots.ptr, d_work.ptr, res, None))
+        R._check(lib.rsm_repair_squares_dev(ctx, d_eds.ptr, d_pres.ptr, k, S, count, pp, d_roots.ptr, d_work.ptr, res, stream))
         got = d_eds.result().reshape(count, W, W, S).copy()
         got_pres = d_pres.result().reshape(count, W, W).copy()
         d_work.result()

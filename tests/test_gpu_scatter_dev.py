@@ -45,6 +45,12 @@ def _batch(k, corrupt_every):
 
 @pytest.mark.parametrize("k,corrupt_every", [(8, 40), (8, 6), (65, 1500), (65, 300)])
 def test_round_trip_on_the_device(lib, k, corrupt_every):
+    round_trip(lib, k, corrupt_every, S)
+
+
+def round_trip(lib, k, corrupt_every, S):
+    """The flow of the module docstring at share size S (tests/test_gpu_share_sizes.py runs
+    it at the other sizes)."""
     W = 2 * k
     ctx = R.device_context(0)
     valid, rr, cr = RP.square(k, S)
